@@ -22,7 +22,14 @@ its rolling window are those of a run that has rendered the settle frames
 already -- as in any longer run of the reference's loop, whose grid never
 stops updating.
 
-Drop-in leg (one GPU, C3-C5, --dropin-leg 1): after the timed region the same
+A plain run does only what `value` needs: world, the 8-frame ray census,
+settle + warm-up, the K timed frames, the outputs (--dump-outputs DIR: the
+last timed frame's colour, motion-vector and depth images as float32 .npy)
+and the result line.  Everything below -- per-stage kernel times and the
+roofline, latencies, the other loop mode, the drop-in leg, the gather check
+and the CPU baseline -- runs only with --full, after the timed region.
+
+Drop-in leg (--full, one GPU, C3-C5, --dropin-leg 1): after the timed region the same
 context renders --steps more frames through renderLoop's own calls
 (rv_update_gi_data, then rv_draw_cuda of that frame's camera; no camera
 look-ahead), timed the same way, reported as "dropin" with its own roofline.
@@ -38,8 +45,8 @@ before touching the GPU and prints rank 0's line.
 
 Loop modes.  `value` is measured in the same loop mode at every N, the one
 N = 1 uses for the config (C4/C5: one pipelined launch per frame; C3: 8-frame
-groups), so a 1 -> 8 curve compares like with like.  For reference frames the
-line also reports the other mode ("modes": per-frame vs grouped 16-frame
+groups), so a 1 -> 8 curve compares like with like.  For reference frames a
+--full line also reports the other mode ("modes": per-frame vs grouped 16-frame
 launches), timed on the same context after the main region.
 """
 from __future__ import annotations
@@ -136,11 +143,50 @@ def bench_config(name, resolution=None, world=None):
     return cfg
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # float32 bytes of one --dump-outputs set
+
+
+def dump_outputs(out_dir, images, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: one frame's images as out_dir/<name>.npy in float32.  `images` maps a name to an
+    (H, W) or (H, W, C) array as rv_readback returns it: RGBA8 bytes are written as 0..255, the
+    R16_FLOAT / R16G16_FLOAT images (uint16 bit patterns) as the half values they hold.  A set of more
+    than `budget` bytes keeps the same pixels of every image, as rows of an (n, C) or (n,) array: a
+    sorted sample without replacement from numpy's default_rng(0), a function of the frame size and the
+    budget alone, so two builds write the same pixels.  Returns what was written, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = next(iter(images.values())).shape[:2]
+    n = h * w
+    per_px = 4 * sum(int(np.prod(a.shape[2:], dtype=np.int64)) for a in images.values())
+    keep = min(n, budget // per_px)
+    idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False)) if keep < n else None
+    arrays = {}
+    for name, a in images.items():
+        assert a.shape[:2] == (h, w), (name, a.shape)
+        if a.dtype == np.uint16:
+            a = a.view(np.float16)
+        if idx is not None:
+            a = a.reshape((n,) + a.shape[2:])[idx]
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        arrays[name] = {"shape": list(a.shape), "non_finite": int(a.size - np.count_nonzero(np.isfinite(a)))}
+    return {"dir": out_dir, "dtype": "float32", "frame": [w, h], "pixels": int(keep),
+            "sample_seed": None if idx is None else 0, "arrays": arrays}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check what `value` does not need: per-stage "
+                         "kernel times and the roofline, single-frame and group latency, the other loop mode "
+                         "(--alt-mode), the drop-in leg (--dropin-leg), the N>1 gather check and the CPU baseline "
+                         "(--cpu-seconds); off: those keys are absent from the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed frame delivered -- the colour, motion-"
+                         "vector and depth images -- as DIR/<name>.npy in float32 (rank 0); above 48 MiB in all, "
+                         "the same fixed, seeded sample of pixels from each image")
     ap.add_argument("--settle", type=int, default=100,
                     help="untimed frames of the same loop before the --warmup frames bring the total untimed "
                          "frames to at least this many (0: off): a 4K frame is ~0.4 ms, and the GPU's clocks and "
@@ -170,7 +216,7 @@ def main():
                          "and assembles every frame); default 1 - 0.019 (N-1): its measured assembly cost is "
                          "1.9%% of a whole frame's render (profiles/r01_shard_probe_c2_root.log)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="CPU-baseline budget (rank 0, N=1); 0 disables")
+                    help="--full: CPU-baseline budget (rank 0, N=1); 0 disables")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (default 0: every core this process may use -- nproc, bounded by a "
                          "cgroup CPU quota)")
@@ -209,8 +255,8 @@ def main():
     ap.add_argument("--flags", type=int, default=None,
                     help="experiments only: override the config's RV_F_* flags")
     ap.add_argument("--alt-mode", type=int, default=1,
-                    help="reference frames, native loop: after the timed region, time the other loop mode (per-frame "
-                         "pipelined launches vs grouped launches of --alt-group frames) and report both under "
+                    help="--full, reference frames, native loop: after the timed region, time the other loop mode "
+                         "(per-frame pipelined launches vs grouped launches of --alt-group frames) and report both under "
                          "\"modes\"; 0 = off")
     ap.add_argument("--alt-group", type=int, default=16,
                     help="frames per launch of the grouped mode the alternate leg times (default 16)")
@@ -218,11 +264,13 @@ def main():
                     help="no GPU: only the rank plumbing (spawn or launcher, gloo process group, barrier, max-over-"
                          "ranks timing) and one JSON line -- the CPU test of --gpus N")
     ap.add_argument("--dropin-leg", type=int, default=1,
-                    help="one GPU, native loop, reference frames (C3-C5): after the timed region, time the same "
+                    help="--full, one GPU, native loop, reference frames (C3-C5): after the timed region, time the same "
                          "number of frames through renderLoop's own calls (rv_update_gi_data, then rv_draw_cuda, "
                          "one frame per call, no knowledge of the next camera: src/main.cpp:119-132) and report "
                          "them as \"dropin\" (ms/frame, cold latency, that loop's roofline); 0 = off")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
 
     # --gpus N: under a launcher WORLD_SIZE must agree; without one, start the N ranks here, before any
     # GPU call (this process never initialises the GPU: it only waits for its children)
@@ -335,7 +383,8 @@ def main():
     w0 = args.warmup                              # the first timed frame of the path
     alt_group = 0 if group >= 2 else max(2, args.alt_group)   # the alternate leg's frames per launch
     n_alt = (args.warmup + args.steps + 2 * max(alt_group, 1) + 5 * alt_group) if args.alt_mode else 0
-    n_path = max(w0 + args.steps + n_stage_frames + 9 + 2 + 5 * max(group, 0) + n_alt, settle + 1)   # + the group-latency calls
+    n_after = (n_stage_frames + 9 + 2 + 5 * max(group, 0) + n_alt) if args.full else 0   # + the group-latency calls
+    n_path = max(w0 + args.steps + n_after, settle + 1)
     pan = args.pan if args.camera == "path" else 0.0
     path = camera_path((pos, yaw, pitch), W, H, n_path, pan=pan, ref_compat=args.camera == "path")
     if args.camera == "static":   # the round-1 bench: one camera, time 0, no jitter
@@ -365,7 +414,7 @@ def main():
     st_stage = {name: mean_stats(r.stats(k)) for k, name in enumerate(rv._lib.STAGES)}
     rays_per_frame = st_all["traces"]
     gi_stats = None
-    if gi_per_frame:   # one UpdateGIData with step counters on: the GI update's algorithmic bytes
+    if gi_per_frame and args.full:   # one UpdateGIData with step counters on: the GI update's algorithmic bytes
         r.set_gi_stats(1)
         r.stats_reset()
         r.update_gi_data()
@@ -537,6 +586,75 @@ def main():
     barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_per_step = elapsed * 1000.0 / args.steps
+    fps = args.steps / elapsed
+    mrays = rays_per_frame * fps / 1e6
+
+    # what the timed path delivered in its last step, before anything else renders into the images
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"color": r.readback(rv.RV_IMAGE_COLOR),
+                                                  "motion": r.readback(rv.RV_IMAGE_MOTION),
+                                                  "depth": r.readback(rv.RV_IMAGE_DEPTH)})
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": f"Mrays/s ({cfg.name}: {cfg.describe}, pose {args.pose}, "
+                      + (f"screen-tile split x{world_size} (RCCL gather))" if world_size > 1 else "1 GPU)"),
+            "value": round(mrays, 2),
+            "unit": "Mrays/s",
+            "n_gpus": world_size,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle_frames": settle,
+            "ms_per_step": round(ms_per_step, 4),
+            "fps": round(fps, 2),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "full": bool(args.full),
+            "data": "synthetic: procedural world from the reference Evaluate (seed 0), camera pose "
+                    f"{args.pose} (reference defaults), random-free",
+            "camera": ("per-frame: yaw pan %g rad/frame from the pose, the reference jitter sequence as "
+                       "drawCUDA maps it with ref_compat (time <- jitterY), previous VP per frame; rays_per_frame "
+                       "= mean of 8 census frames of the timed path" % pan) if args.camera == "path"
+                      else "static: one camera, time 0, no jitter",
+            "config": {"workload": cfg.name, "world": f"{cfg.n}^3", "resolution": f"{W}x{H}",
+                       "flags": flags, "gi_sweeps": cfg.gi_sweeps, "gi_update_per_frame": gi_per_frame,
+                       "parallelism": f"screen-tiles {T}px x{world_size}" if world_size > 1 else "single-gpu"},
+            "rays_per_frame": rays_per_frame,
+            # SURVEY s8d: cone marches are reported separately
+            "cone_steps_per_frame": st_all["cone_steps"],
+            "cone_steps_per_s": round(st_all["cone_steps"] * fps, 1),
+            "path": args.path, "gi_async": bool(args.gi_async), "frames_in_flight": nfl,
+            "loop": "native" if native else "python",
+            "gather": ("rccl" if native else args.dist_backend) if world_size > 1 else None,
+            "root_weight": root_weight if world_size > 1 and native else None,
+            "outputs": dumped,
+            "world_build_s": round(world_s, 3),
+            "tex_table_bytes": int(r.tex_table_info()[1]),
+            "stats": st_all,
+        }
+
+    def finish_run():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if comm is not None:
+            comm.close()
+        r.close()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:   # a plain run ends here; the rest of main() is --full's
+        if args.dump and rank == 0:
+            write_png(args.dump, r.readback(rv.RV_IMAGE_COLOR))
+        return finish_run()
 
     # Per-stage kernel times from HIP events on the context's streams, in a
     # separate pass of the same loop after the timed region, one record per
@@ -575,10 +693,6 @@ def main():
     launches = r.timing_launches()
     r.timing_enable(0)
     barrier()
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
 
     # single-frame latency: one frame per call, submitted and waited for alone (median of 9)
     # (the per-frame loops: the frame's UpdateGIData + drawCUDA calls from an idle device to completion)
@@ -671,10 +785,6 @@ def main():
     if args.dump and rank == 0:
         write_png(args.dump, r.readback(rv.RV_IMAGE_COLOR))
 
-    ms_per_step = elapsed * 1000.0 / args.steps
-    fps = args.steps / elapsed
-    mrays = rays_per_frame * fps / 1e6
-
     # average launch time per stage, and its share of a frame
     avg_stage_ms = {k: (per_stage_ms[k] / launches[k] if launches[k] else 0.0) for k in per_stage_ms}
     frame_stage_ms = {k: avg_stage_ms[k] / stage_fpl[k] for k in avg_stage_ms}
@@ -753,41 +863,13 @@ def main():
         cpu = cpu_baseline(r, cfg, path[w0], flags, atlas, args.cpu_seconds, args.cpu_threads)
 
     if rank == 0:
-        line = {
-            "metric": f"Mrays/s ({cfg.name}: {cfg.describe}, pose {args.pose}, "
-                      + (f"screen-tile split x{world_size} (RCCL gather))" if world_size > 1 else "1 GPU)"),
-            "value": round(mrays, 2),
-            "unit": "Mrays/s",
-            "n_gpus": world_size,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_frames": settle,
-            "ms_per_step": round(ms_per_step, 4),
-            "fps": round(fps, 2),
+        line.update({
             "latency_ms": latency_ms,
             "latency_mode": latency_mode,
             "group_latency_ms": group_latency_ms,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic: procedural world from the reference Evaluate (seed 0), camera pose "
-                    f"{args.pose} (reference defaults), random-free",
-            "camera": ("per-frame: yaw pan %g rad/frame from the pose, the reference jitter sequence as "
-                       "drawCUDA maps it with ref_compat (time <- jitterY), previous VP per frame; rays_per_frame "
-                       "= mean of 8 census frames of the timed path" % pan) if args.camera == "path"
-                      else "static: one camera, time 0, no jitter",
-            "config": {"workload": cfg.name, "world": f"{cfg.n}^3", "resolution": f"{W}x{H}",
-                       "flags": flags, "gi_sweeps": cfg.gi_sweeps, "gi_update_per_frame": gi_per_frame,
-                       "parallelism": f"screen-tiles {T}px x{world_size}" if world_size > 1 else "single-gpu"},
-            "rays_per_frame": rays_per_frame,
-            # SURVEY s8d: cone marches are reported separately
-            "cone_steps_per_frame": st_all["cone_steps"],
-            "cone_steps_per_s": round(st_all["cone_steps"] * fps, 1),
             "stage_ms": {"gi_update": round(gi_ms, 4), "prepass": round(pp_ms, 4), "render": round(render_ms, 4)},
             "frames_per_launch": {k: v for k, v in stage_fpl.items() if launches.get(k)},
             "kernel_ms": {k: round(v, 4) for k, v in avg_stage_ms.items()},   # per launch
-            "path": args.path, "gi_async": bool(args.gi_async), "frames_in_flight": nfl,
             "pipelined": bool(piped),
             "flow": bool(flowed),
             # render waves of the flow launches that stopped waiting for their pre-pass tiles and evaluated
@@ -796,23 +878,12 @@ def main():
             "frame_group": ref_group,
             # both loop modes of the reference frame (value = the "is_value" one, the mode N = 1 runs)
             "modes": modes,
-            "loop": "native" if native else "python",
-            "gather": ("rccl" if native else args.dist_backend) if world_size > 1 else None,
-            "root_weight": root_weight if world_size > 1 and native else None,
             "gather_check": gather_check,
             "roofline": roofline,
             "dropin": dropin,
             "cpu_baseline": cpu,
-            "world_build_s": round(world_s, 3),
-            "tex_table_bytes": int(r.tex_table_info()[1]),
-            "stats": st_all,
-        }
-        print(json.dumps(line), flush=True)
-    if comm is not None:
-        comm.close()
-    r.close()
-    if dist is not None:
-        dist.destroy_process_group()
+        })
+    return finish_run()
 
 
 def spawn_ranks(n: int, argv) -> int:

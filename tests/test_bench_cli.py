@@ -92,8 +92,73 @@ def test_world_override():
         bench.bench_config("c4", world=12)
 
 
+def _bench():
+    import importlib
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    return importlib.import_module("bench")
+
+
+def _frame_images(w, h, seed):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    return {"color": rng.integers(0, 256, (h, w, 4), dtype=np.uint8),
+            "motion": rng.uniform(-2, 2, (h, w, 2)).astype(np.float16).view(np.uint16),
+            "depth": rng.uniform(0, 1, (h, w)).astype(np.float16).view(np.uint16)}
+
+
+def test_dump_outputs_small_frame_is_written_whole(tmp_path):
+    """--dump-outputs: a frame inside the budget is written whole, float32, RGBA8 as 0..255 and the
+    half-float images as their values."""
+    import numpy as np
+    bench = _bench()
+    im = _frame_images(37, 21, 1)
+    info = bench.dump_outputs(str(tmp_path / "o"), im)
+    assert info["pixels"] == 37 * 21 and info["sample_seed"] is None
+    got = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in im}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["color"], im["color"].astype(np.float32))
+    assert np.array_equal(got["motion"], im["motion"].view(np.float16).astype(np.float32))
+    assert got["depth"].shape == (21, 37) and info["arrays"]["depth"] == {"shape": [21, 37], "non_finite": 0}
+
+
+def test_dump_outputs_large_frame_is_a_fixed_sample(tmp_path):
+    """A 4K frame exceeds the budget: every image keeps the same sorted, seeded pixel sample, the same from
+    call to call, and the whole set stays under 64 MB."""
+    import numpy as np
+    bench = _bench()
+    w, h = 3840, 2160
+    im = _frame_images(w, h, 2)
+    a = bench.dump_outputs(str(tmp_path / "a"), im)
+    im2 = {k: v.copy() for k, v in im.items()}
+    im2["color"][::7, ::5] ^= 1          # another build's frame: the sample must not depend on the data
+    b = bench.dump_outputs(str(tmp_path / "b"), im2)
+    assert a["pixels"] == b["pixels"] == bench.DUMP_BUDGET_BYTES // 28 < w * h and a["sample_seed"] == 0
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 1000 * 1000
+    idx = np.sort(np.random.default_rng(0).choice(w * h, size=a["pixels"], replace=False))
+    for n in im:
+        ga, gb = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert ga.dtype == np.float32 and ga.shape[0] == a["pixels"]
+        src = im[n].view(np.float16) if im[n].dtype == np.uint16 else im[n]
+        assert np.array_equal(ga, src.reshape((w * h,) + src.shape[2:])[idx].astype(np.float32))
+        src2 = im2[n].view(np.float16) if im2[n].dtype == np.uint16 else im2[n]
+        assert np.array_equal(gb, src2.reshape((w * h,) + src2.shape[2:])[idx].astype(np.float32))
+
+
+def test_plain_and_full_options(tmp_path):
+    """--full and --dump-outputs exist, and --steps 0 is refused (it must set the number of timed steps)."""
+    p = _run(["--help"], _env())
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = _run(["--rehearse", "--steps", "0"], _env())
+    assert p.returncode == 2 and "--steps" in p.stderr
+    p = _run(["--rehearse", "--steps", "3", "--full", "--dump-outputs", str(tmp_path / "d")], _env())
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads(p.stdout.strip().splitlines()[-1])["steps"] == 3
+
+
 def test_recorded_bench_line_keeps_the_contract():
-    """The bench line the driver parses, as last recorded on the GPU (profiles/r06/final/driver_bench.json):
+    """The --full bench line, as last recorded on the GPU (profiles/r06/final/driver_bench.json):
     every contract key, the roofline object (algorithmic bytes / launch time against the 8 TB/s peak,
     with the PMC traffic) and the CPU baseline object."""
     path = os.path.join(ROOT, "profiles", "r06", "final", "driver_bench.json")

@@ -61,7 +61,7 @@ tests)
 bench)
     for spec in "$@"; do
         name=${spec%%:*}; args=$(echo "${spec#*:}" | tr '_' ' ')
-        run "bench_$name" 300 python bench.py $args --steps "$STEPS" --warmup "$WARMUP"
+        run "bench_$name" 300 python bench.py --full $args --steps "$STEPS" --warmup "$WARMUP"
         grep '^{' "gpurun_out/${TAG}_bench_$name.log" | tail -1 > "gpurun_out/${TAG}_bench_$name.json"
         summary "$name" "gpurun_out/${TAG}_bench_$name.json"
     done ;;
@@ -89,7 +89,7 @@ prof)
         name=${spec%%:*}; args=$(echo "${spec#*:}" | tr '_' ' ')
         rm -rf "gpurun_out/${TAG}_prof_$name"
         run "prof_$name" 300 rocprofv3 --kernel-trace --stats --output-format csv -d "gpurun_out/${TAG}_prof_$name" -o run \
-            -- python3 bench.py $args --cpu-seconds 0
+            -- python3 bench.py --full $args --cpu-seconds 0
         grep '^{' "gpurun_out/${TAG}_prof_$name.log" | tail -1 > "gpurun_out/${TAG}_prof_$name/bench_line.json"
     done ;;
 ab)
@@ -100,7 +100,7 @@ ab)
             IFS=: read -r name envs args <<< "$spec"
             args=$(echo "$args" | tr '_' ' ')
             envv=(); [ "$envs" != "-" ] && IFS=, read -r -a envv <<< "$envs"
-            run "ab_$name" 300 env "${envv[@]}" python bench.py $args --steps "$STEPS" --warmup "$WARMUP" --cpu-seconds 0 \
+            run "ab_$name" 300 env "${envv[@]}" python bench.py --full $args --steps "$STEPS" --warmup "$WARMUP" --cpu-seconds 0 \
                 --dropin-leg 0
             ms=$(grep '^{' "gpurun_out/${TAG}_ab_$name.log" | tail -1 | python3 -c \
                  "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['avg_launch_ms'], d['latency_ms'])")
