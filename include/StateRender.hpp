@@ -79,6 +79,10 @@ public:
     // CoarseArray::UpdateGIData: RAYPS cells per call, rolling offset
     void updateGIData() { check(rv_update_gi_data(ctx_), ctx_, "rv_update_gi_data"); }
 
+    // Place / break blocks (no reference counterpart: its world is fixed after CArray::fill): voxel
+    // boxes set or cleared in place, the CSDF and the early exits rebuilt around them (rv_world_edit)
+    void editWorld(const rv_edit_box* boxes, int n) { check(rv_world_edit(ctx_, boxes, n), ctx_, "rv_world_edit"); }
+
     // StateRender::drawCUDA, identical parameter list and order
     void drawCUDA(const vec3& pos, const vec3& fo, const vec3& up, const vec3& ri,
                   mat4* unjitteredViewProjectionMatrix, mat4* prevUnjitteredViewProjectionMatrix,

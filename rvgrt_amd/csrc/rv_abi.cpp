@@ -158,6 +158,7 @@ void rv_destroy(rv_ctx* c) {
     hipFree(c->counters);
     hipFree(c->d_top);
     hipFree(c->coltop);
+    hipFree(c->edit_boxes); hipFree(c->edit_flag); hipFree(c->edit_t0); hipFree(c->edit_t1);
     hipFree(c->tiles.d); hipFree(c->untile_ids.d);
     hipFree(c->tilebuf);
     hipFree(c->hpos); hipFree(c->hinfo); hipFree(c->hsec); hipFree(c->pphit); hipFree(c->qcount);
@@ -457,7 +458,7 @@ static rv_status tex_table(rv_ctx* c) {
 // The sky exit of the frame traversal (World::ytop, rv_device.h trace): the highest solid voxel
 // row + 2, and the sun exit of its shadow rays (World::horizon), recomputed after every write of the
 // bits.  rv_config.exits_off & RV_EXIT_SKY turns all three exits off (ytop = Y, no horizon, no skip).
-static rv_status world_top(rv_ctx* c) {
+RV_HIDDEN rv_status world_top(rv_ctx* c) {
     c->w.ytop = (uint32_t)c->w.Y;
     uint32_t* hz = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->brick) + horizon_byte(c->w.coff));
     const size_t hzb = horizon_bytes(c->w.X, c->w.Z);

@@ -1,9 +1,10 @@
 // rv_host.h -- internal to librvgrt_hip.so (not installed): the context (rv_ctx), the communicator and
-// the host helpers shared by the three parts of the C ABI declared in include/rvgrt.h --
+// the host helpers shared by the four parts of the C ABI declared in include/rvgrt.h --
 //   rv_abi.cpp    contexts, world build / import / export, the GI update, single frames (flow frames,
 //                 drawCUDA), readback, stats;
 //   rv_loops.cpp  the native frame loops (batched, pipelined, grouped), tile shards;
-//   rv_comm.cpp   the transport: RCCL resolved at run time, or the in-process loopback group.
+//   rv_comm.cpp   the transport: RCCL resolved at run time, or the in-process loopback group;
+//   rv_edit.cpp   voxel edits in place (rv_world_edit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -214,6 +215,13 @@ struct rv_ctx {
     hipEvent_t cam_ev = nullptr; bool cam_pending = false;
     uint64_t gi_swapped_at = 0;    // frame_seq at the last GI buffer flip: older frames read gi_tmp
     hipStream_t world_stream = nullptr;   // stream ev_world was recorded on
+    // rv_world_edit: the boxes' device copy (and the stable host copy it is uploaded from), the
+    // "a word changed" flag, the local CSDF passes' scratch (kept while small) and rv_world_edit_info's record
+    std::vector<rv_edit_box> edit_h;
+    rv_edit_box* edit_boxes = nullptr; size_t edit_boxes_cap = 0;
+    uint32_t* edit_flag = nullptr;
+    uint8_t* edit_t0 = nullptr; uint8_t* edit_t1 = nullptr; size_t edit_t0_cap = 0, edit_t1_cap = 0;
+    uint64_t edit_count = 0, edit_cells = 0; int edit_full = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;
@@ -428,6 +436,7 @@ extern "C" {
 RV_HIDDEN rv_status end_frame(rv_ctx* c);
 RV_HIDDEN rv_status wait_all_frames(rv_ctx* c);   // every frame in flight and the last world/GI write
 RV_HIDDEN rv_status mark_world(rv_ctx* c);        // a world/GI write: versions bumped, ev_world recorded
+RV_HIDDEN rv_status world_top(rv_ctx* c);         // the exact early exits from the bits, after every write of them
 RV_HIDDEN rv_status upload_ids(rv_ctx* c, DevIds& ids, const int32_t* src, int n, bool* changed);
 RV_HIDDEN FrameParams make_params_d(rv_ctx* c, const rv_frame_desc& d, int32_t flags);
 RV_HIDDEN rv_status upload_cams(rv_ctx* c, const Seq& q, hipStream_t st, const FrameCam** out,

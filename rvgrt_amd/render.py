@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import RvError, rv_camera, rv_config, rv_frame_desc, rv_hit, rv_stats
+from ._lib import RvError, rv_camera, rv_config, rv_edit_box, rv_frame_desc, rv_hit, rv_stats
 
 
 def _ptr(a: np.ndarray):
@@ -51,6 +51,31 @@ def camera_dict(cam: rv_camera, vp):
     return {"pos": np.array(cam.pos[:], np.float32), "fo": np.array(cam.forward[:], np.float32),
             "ri": np.array(cam.right[:], np.float32), "up": np.array(cam.up[:], np.float32),
             "vp": np.asarray(vp, np.float32)}
+
+
+def _edit_boxes(boxes):
+    """ctypes array of rv_edit_box from tuples (x0, y0, z0, x1, y1, z1, solid)."""
+    arr = (rv_edit_box * max(len(boxes), 1))()
+    for i, b in enumerate(boxes):
+        if len(b) != 7:
+            raise ValueError("an edit box is (x0, y0, z0, x1, y1, z1, solid)")
+        arr[i] = rv_edit_box(*(int(v) for v in b))
+    return arr
+
+
+def edit_region(log2_dims, boxes):
+    """rv_world_edit_region (host only): the coarse-cell box (cx0, cx1, cy0, cy1,
+    cz0, cz1) whose CSDF bytes world_edit(boxes) recomputes locally in a world
+    of these log2 dims, and its volume."""
+    L = _lib.load()
+    boxes = list(boxes)
+    region = (C.c_int32 * 6)()
+    cells = C.c_uint64()
+    st = L.rv_world_edit_region(int(log2_dims[0]), int(log2_dims[1]), int(log2_dims[2]), _edit_boxes(boxes),
+                                len(boxes), region, C.byref(cells))
+    if st != 0:
+        raise RvError(f"rv_world_edit_region: {_lib.STATUS_NAMES.get(st, st)}")
+    return tuple(region), int(cells.value)
 
 
 def rccl_path():
@@ -283,6 +308,20 @@ class StateRender:
             a = np.zeros((X // 4) * (Y // 4) * (Z // 4) * 4, np.uint8)
         self._check(self._L.rv_world_export(self._h, kind, _ptr(a), a.nbytes), "rv_world_export")
         return a
+
+    def world_edit(self, boxes):
+        """rv_world_edit: set / clear voxel boxes (x0, y0, z0, x1, y1, z1, solid) in
+        place, in order; bits, CSDF and exits end as a bits import + csdf_build
+        of the edited world would leave them."""
+        boxes = list(boxes)
+        self._check(self._L.rv_world_edit(self._h, _edit_boxes(boxes), len(boxes)), "rv_world_edit")
+
+    def world_edit_info(self):
+        """(edits, csdf_cells, last_full): calls that changed a voxel, the coarse
+        cells the last call recomputed, whether it ran the whole-grid build."""
+        e, n, f = C.c_uint64(), C.c_uint64(), C.c_int32()
+        self._check(self._L.rv_world_edit_info(self._h, C.byref(e), C.byref(n), C.byref(f)), "rv_world_edit_info")
+        return int(e.value), int(n.value), bool(f.value)
 
     # ------------------------------------------------------------ frames
     def draw_cuda(self, pos, fo, up, ri, vp, prev_vp, jitter_x=0.0, jitter_y=0.0):
