@@ -122,13 +122,16 @@ __device__ __forceinline__ bool sched_block(int sched, const int* order, uint32_
     return by < nby;
 }
 
+// a wave's lifetime since t0 as a cost: 10-ns ticks + 1, saturated (0 = not rendered)
+__device__ __forceinline__ uint32_t cost_ticks(uint64_t t0) {
+    const uint64_t dt = wall_clock64() - t0;
+    return (uint32_t)(dt > 0xFFFFFFFEull ? 0xFFFFFFFEull : dt) + 1u;
+}
 // SCHED_COST feedback: every wave reports its lifetime to its chunk.
 template <uint32_t BW, uint32_t BH>
 __device__ __forceinline__ void chunk_cost_report(uint32_t* cost, uint64_t t0, uint32_t w, uint32_t bx, uint32_t by) {
     if (!cost || (threadIdx.x & 63) != 0) return;
-    uint64_t dt = wall_clock64() - t0;
-    atomicMax(&cost[(by * BH / CHUNK_PX) * chunks_x(w) + bx * BW / CHUNK_PX],
-              (uint32_t)(dt > 0xFFFFFFFEull ? 0xFFFFFFFEull : dt) + 1u);
+    atomicMax(&cost[(by * BH / CHUNK_PX) * chunks_x(w) + bx * BW / CHUNK_PX], cost_ticks(t0));
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

@@ -146,7 +146,7 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
     } else {
         if (rv_status s = edit_reserve(c, c->edit_t0, c->edit_t0_cap, (size_t)p.rs.cells())) return s;
         if (rv_status s = edit_reserve(c, c->edit_t1, c->edit_t1_cap, (size_t)p.rx.cells())) return s;
-        launch_edit_csdf(c->stream, c->brick, current_world(c), p.rs, p.rx, p.ry, p.rf, c->edit_t0, c->edit_t1);
+        launch_csdf_box(c->stream, c->brick, current_world(c), p.rs, p.rx, p.ry, p.rf, c->edit_t0, c->edit_t1);
         LAUNCH_CHECK(c);
         const hipError_t se = hipStreamSynchronize(c->stream);
         if (c->edit_t0_cap + c->edit_t1_cap > EDIT_SCRATCH_KEEP) {
