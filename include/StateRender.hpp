@@ -82,6 +82,11 @@ public:
     // Place / break blocks (no reference counterpart: its world is fixed after CArray::fill): voxel
     // boxes set or cleared in place, the CSDF and the early exits rebuilt around them (rv_world_edit)
     void editWorld(const rv_edit_box* boxes, int n) { check(rv_world_edit(ctx_, boxes, n), ctx_, "rv_world_edit"); }
+    // The GI cells of a box refreshed at once after an edit: `iterations` update steps with RNG frames
+    // frame0, frame0 + 1, ... (rv_gi_relight; rv_gi_relight_box picks the box around the edit)
+    void relightGI(const rv_gi_box& box, uint32_t frame0, int iterations, bool init = false) {
+        check(rv_gi_relight(ctx_, &box, frame0, iterations, init ? RV_RELIGHT_INIT : 0), ctx_, "rv_gi_relight");
+    }
 
     // StateRender::drawCUDA, identical parameter list and order
     void drawCUDA(const vec3& pos, const vec3& fo, const vec3& up, const vec3& ri,

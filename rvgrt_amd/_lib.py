@@ -64,6 +64,15 @@ class rv_edit_box(C.Structure):
 
 RV_EDIT_MAX_BOXES = 1024
 
+
+class rv_gi_box(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32),
+                ("x1", C.c_int32), ("y1", C.c_int32), ("z1", C.c_int32)]
+
+
+RV_RELIGHT_INIT = 1
+RV_RELIGHT_MAX_RECORDS = 1 << 23
+
 STAT_FIELDS = ["traces", "primary", "shadow", "refl", "refl_shadow", "prepass_primary",
                "prepass_shadow", "cones", "cone_steps", "sphere_steps", "dda_steps",
                "csdf_checks", "tex_samples", "undef_hits", "gi_traces", "frames"]
@@ -108,6 +117,9 @@ SIGNATURES = [
     ("rv_world_edit_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     ("rv_world_edit_region", I32, [I32, I32, I32, C.POINTER(rv_edit_box), I32, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_uint64)]),
+    ("rv_gi_relight", I32, [P, C.POINTER(rv_gi_box), U32, I32, I32]),
+    ("rv_gi_relight_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rv_gi_relight_box", I32, [I32, I32, I32, C.POINTER(rv_edit_box), I32, I32, C.POINTER(rv_gi_box)]),
     ("rv_gi_update", I32, [P, U32, U64, U64]),
     ("rv_update_gi_data", I32, [P]),
     ("rv_draw_cuda", I32, [P, P, P, P, P, P, P, F, F]),

@@ -3,6 +3,22 @@
 // (rv_world_edit_region).  The kernels are in rv_edit.hip.
 #include "rv_host.h"
 
+// shared with rv_relight.cpp
+bool dims_ok(int lx, int ly, int lz) {   // rv_create's limits
+    return lx >= 4 && ly >= 4 && lz >= 4 && lx <= 13 && ly <= 13 && lz <= 13 && lx + ly + lz <= 34;
+}
+
+bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n) {
+    if (n < 0 || n > RV_EDIT_MAX_BOXES || (n > 0 && !b)) return false;
+    const int X = 1 << lx, Y = 1 << ly, Z = 1 << lz;
+    for (int i = 0; i < n; i++) {
+        if (b[i].x0 < 0 || b[i].y0 < 0 || b[i].z0 < 0 || b[i].x1 > X || b[i].y1 > Y || b[i].z1 > Z) return false;
+        if (b[i].x1 <= b[i].x0 || b[i].y1 <= b[i].y0 || b[i].z1 <= b[i].z0) return false;
+        if (b[i].solid != 0 && b[i].solid != 1) return false;
+    }
+    return true;
+}
+
 namespace {
 
 // What one rv_world_edit call touches.
@@ -27,21 +43,6 @@ struct EditPlan {
     uint64_t local_cells;    // cells the four local passes visit
     uint64_t full_cells;     // cells the four whole-grid passes visit
 };
-
-bool dims_ok(int lx, int ly, int lz) {   // rv_create's limits
-    return lx >= 4 && ly >= 4 && lz >= 4 && lx <= 13 && ly <= 13 && lz <= 13 && lx + ly + lz <= 34;
-}
-
-bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n) {
-    if (n < 0 || n > RV_EDIT_MAX_BOXES || (n > 0 && !b)) return false;
-    const int X = 1 << lx, Y = 1 << ly, Z = 1 << lz;
-    for (int i = 0; i < n; i++) {
-        if (b[i].x0 < 0 || b[i].y0 < 0 || b[i].z0 < 0 || b[i].x1 > X || b[i].y1 > Y || b[i].z1 > Z) return false;
-        if (b[i].x1 <= b[i].x0 || b[i].y1 <= b[i].y0 || b[i].z1 <= b[i].z0) return false;
-        if (b[i].solid != 0 && b[i].solid != 1) return false;
-    }
-    return true;
-}
 
 CellBox grown(const int e0[3], const int e1[3], const int S[3], int gx, int gy, int gz) {
     const int g[3] = {gx, gy, gz};
@@ -75,16 +76,6 @@ EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
 
 // Scratch of the local passes is kept between edits while it is small (a single block's is 26 MB).
 constexpr size_t EDIT_SCRATCH_KEEP = (size_t)64 << 20;
-
-rv_status edit_reserve(rv_ctx* c, uint8_t*& p, size_t& cap, size_t need) {
-    if (need <= cap) return RV_OK;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&p, need));
-    cap = need;
-    return RV_OK;
-}
 
 }  // namespace
 
@@ -144,8 +135,8 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
         c->edit_cells = n_csdf(c);
         c->edit_full = 1;
     } else {
-        if (rv_status s = edit_reserve(c, c->edit_t0, c->edit_t0_cap, (size_t)p.rs.cells())) return s;
-        if (rv_status s = edit_reserve(c, c->edit_t1, c->edit_t1_cap, (size_t)p.rx.cells())) return s;
+        if (rv_status s = dev_reserve(c, c->edit_t0, c->edit_t0_cap, (size_t)p.rs.cells())) return s;
+        if (rv_status s = dev_reserve(c, c->edit_t1, c->edit_t1_cap, (size_t)p.rx.cells())) return s;
         launch_csdf_box(c->stream, c->brick, current_world(c), p.rs, p.rx, p.ry, p.rf, c->edit_t0, c->edit_t1);
         LAUNCH_CHECK(c);
         const hipError_t se = hipStreamSynchronize(c->stream);

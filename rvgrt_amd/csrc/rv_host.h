@@ -1,10 +1,11 @@
 // rv_host.h -- internal to librvgrt_hip.so (not installed): the context (rv_ctx), the communicator and
-// the host helpers shared by the four parts of the C ABI declared in include/rvgrt.h --
+// the host helpers shared by the parts of the C ABI declared in include/rvgrt.h --
 //   rv_abi.cpp    contexts, world build / import / export, the GI update, single frames (flow frames,
 //                 drawCUDA), readback, stats;
 //   rv_loops.cpp  the native frame loops (batched, pipelined, grouped), tile shards;
 //   rv_comm.cpp   the transport: RCCL resolved at run time, or the in-process loopback group;
-//   rv_edit.cpp   voxel edits in place (rv_world_edit).
+//   rv_edit.cpp   voxel edits in place (rv_world_edit);
+//   rv_relight.cpp  the GI refresh of a cell box (rv_gi_relight).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -222,6 +223,11 @@ struct rv_ctx {
     uint32_t* edit_flag = nullptr;
     uint8_t* edit_t0 = nullptr; uint8_t* edit_t1 = nullptr; size_t edit_t0_cap = 0, edit_t1_cap = 0;
     uint64_t edit_count = 0, edit_cells = 0; int edit_full = 0;
+    // rv_gi_relight: the steps' records and the box's two dense value arrays (kept between calls; caps in bytes),
+    // rv_gi_relight_info's sums
+    uint2* relight_rec = nullptr; size_t relight_rec_cap = 0;
+    uint32_t* relight_dense[2] = {nullptr, nullptr}; size_t relight_dense_cap[2] = {0, 0};
+    uint64_t relight_calls = 0, relight_cells = 0, relight_records = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;
@@ -316,6 +322,18 @@ inline rv_status fail(rv_ctx* c, rv_status s, const std::string& msg) {
     } while (0)
 
 #define LAUNCH_CHECK(ctx) HIP_TRY(ctx, hipGetLastError())
+
+// Grows a device array the context keeps between calls to `need` bytes (its contents are not kept).
+template <class T>
+inline rv_status dev_reserve(rv_ctx* c, T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return RV_OK;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(c, hipMalloc((void**)&p, need));
+    cap = need;
+    return RV_OK;
+}
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -444,6 +462,10 @@ RV_HIDDEN rv_status upload_cams(rv_ctx* c, const Seq& q, hipStream_t st, const F
 RV_HIDDEN rv_status run_stages(rv_ctx* c, FrameParams f, bool tiles, int which = 3);
 RV_HIDDEN rv_status tile_list(rv_ctx* c, const int32_t* tile_ids, int32_t ntiles, int32_t tile_px);
 }
+
+// rv_edit.cpp: rv_create's limits on the world dims; a box list's validity in such a world
+RV_HIDDEN bool dims_ok(int lx, int ly, int lz);
+RV_HIDDEN bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n);
 
 // rv_comm.cpp: the four exchange operations of the loops and the bounded wait
 RV_HIDDEN double comm_timeout_s();

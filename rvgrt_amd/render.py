@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import RvError, rv_camera, rv_config, rv_edit_box, rv_frame_desc, rv_hit, rv_stats
+from ._lib import RvError, rv_camera, rv_config, rv_edit_box, rv_frame_desc, rv_gi_box, rv_hit, rv_stats
 
 
 def _ptr(a: np.ndarray):
@@ -76,6 +76,21 @@ def edit_region(log2_dims, boxes):
     if st != 0:
         raise RvError(f"rv_world_edit_region: {_lib.STATUS_NAMES.get(st, st)}")
     return tuple(region), int(cells.value)
+
+
+def relight_box(log2_dims, boxes, margin=0):
+    """rv_gi_relight_box (host only): the GI-cell box (x0, y0, z0, x1, y1, z1) around
+    the edit boxes' voxels, grown by `margin` cells per axis and clipped to the
+    grid of a world of these log2 dims -- what to hand to gi_relight after
+    world_edit(boxes)."""
+    L = _lib.load()
+    boxes = list(boxes)
+    out = rv_gi_box()
+    st = L.rv_gi_relight_box(int(log2_dims[0]), int(log2_dims[1]), int(log2_dims[2]), _edit_boxes(boxes),
+                             len(boxes), int(margin), C.byref(out))
+    if st != 0:
+        raise RvError(f"rv_gi_relight_box: {_lib.STATUS_NAMES.get(st, st)}")
+    return (out.x0, out.y0, out.z0, out.x1, out.y1, out.z1)
 
 
 def rccl_path():
@@ -322,6 +337,23 @@ class StateRender:
         e, n, f = C.c_uint64(), C.c_uint64(), C.c_int32()
         self._check(self._L.rv_world_edit_info(self._h, C.byref(e), C.byref(n), C.byref(f)), "rv_world_edit_info")
         return int(e.value), int(n.value), bool(f.value)
+
+    def gi_relight(self, box, frame0, iterations, init=False):
+        """rv_gi_relight: `iterations` update steps (RNG frames frame0, frame0 + 1, ...)
+        of the GI cells (x0, y0, z0, x1, y1, z1), each step reading the grid the step
+        before left; init=True first gives the box's cells gi_init's values.  The
+        GI frame counter and the rolling offset are untouched."""
+        if len(box) != 6:
+            raise ValueError("a GI box is (x0, y0, z0, x1, y1, z1)")
+        b = rv_gi_box(*(int(v) for v in box))
+        self._check(self._L.rv_gi_relight(self._h, C.byref(b), int(frame0) & 0xFFFFFFFF, int(iterations),
+                                          _lib.RV_RELIGHT_INIT if init else 0), "rv_gi_relight")
+
+    def gi_relight_info(self):
+        """(calls, cells, records): sums over the gi_relight calls that did work."""
+        n, c, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.rv_gi_relight_info(self._h, C.byref(n), C.byref(c), C.byref(r)), "rv_gi_relight_info")
+        return int(n.value), int(c.value), int(r.value)
 
     # ------------------------------------------------------------ frames
     def draw_cuda(self, pos, fo, up, ri, vp, prev_vp, jitter_x=0.0, jitter_y=0.0):
