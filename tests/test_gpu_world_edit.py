@@ -121,6 +121,7 @@ def test_unaligned_overlapping_boxes_and_full_fallback(rv, oracle, oracle_world)
         boxes.append((x, y, z, x + 1, y + 1, z + 1, (q >> 1) & 1))
     boxes.append((2 * fx + 1, 2 * fy, 2 * fz + 1, 2 * fx + 2, 2 * fy + 1, 2 * fz + 2, 0))
     r.world_edit(boxes)
+    assert r.world_edit_info()[2] is True   # 64^3 cells: every region covers the grid
     _twin_edit(rv, t, lg, boxes)
     ow = oracle.OracleWorld(*lg)
     ow.bits[:] = _edited(bits0, lg, boxes)
