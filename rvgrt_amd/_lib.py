@@ -21,7 +21,7 @@ RV_WORLD_BITS, RV_WORLD_CSDF, RV_WORLD_GI = range(3)
 RV_PATH_FUSED, RV_PATH_WAVEFRONT = 0, 1
 # rv_set_option (include/rvgrt.h rv_option)
 RV_OPT_PIPE_ORDER, RV_OPT_BATCH_STREAMS, RV_OPT_FLOW_SPIN, RV_OPT_FLOW_FORCE_FALLBACK, RV_OPT_GI_PAIRS, \
-    RV_OPT_GI_SHARD_PROBE = range(1, 7)
+    RV_OPT_GI_SHARD_PROBE, RV_OPT_PIPE_MIX, RV_OPT_PIPE_MIX_LAST = range(1, 9)
 # rv_config.exits_off bits
 RV_EXIT_SKY, RV_EXIT_COLUMN, RV_EXIT_SUN = 1, 2, 4
 
@@ -97,6 +97,7 @@ SIGNATURES = [
     ("rv_set_stream", I32, [P, P]),
     ("rv_set_option", I32, [P, I32, C.c_int64]),
     ("rv_get_option", I32, [P, I32, C.POINTER(C.c_int64)]),
+    ("rv_pipe_layout_map", I32, [C.c_int64, C.c_int64, C.POINTER(U32), U32, U32, P, P]),
     ("rv_set_frame_path", I32, [P, I32]),
     ("rv_tile_shard_assign", I32, [I32, I32, I32, I32, C.c_float, P]),
     ("rv_set_gi_async", I32, [P, I32]),

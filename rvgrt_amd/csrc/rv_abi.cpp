@@ -104,6 +104,10 @@ rv_status rv_create(const rv_config* cfg, int32_t device, rv_ctx** out) {
         hipStreamCreateWithPriority(&c->gi_stream, hipStreamNonBlocking, gi_prio(c)) != hipSuccess)
         return cleanup_fail(RV_ERR_HIP, "gi stream/events");
     if (hipDeviceSynchronize() != hipSuccess) return cleanup_fail(RV_ERR_HIP, "init sync");
+    if (const char* e = getenv("RV_PIPE_MIX")) {   // A/B runs: RV_OPT_PIPE_MIX's packed value (any base)
+        const long long v = strtoll(e, nullptr, 0);
+        if (v >= 0 && (v >> 24) <= 0xFFFFFF) { c->pipe_mix = (uint64_t)v; c->pipe_mix_set = true; }
+    }
     *out = c;
     return RV_OK;
 }
@@ -216,6 +220,13 @@ rv_status rv_set_option(rv_ctx* c, int32_t opt, int64_t v) {
         c->carry_gi = c->carry_pp = false;
         return RV_OK;
     }
+    case RV_OPT_PIPE_MIX:
+        if (v < 0 || (v >> 24) > 0xFFFFFF) return fail(c, RV_ERR_INVALID, "RV_OPT_PIPE_MIX: head rows above 2^24");
+        c->pipe_mix = (uint64_t)v;
+        c->pipe_mix_set = true;
+        return RV_OK;
+    case RV_OPT_PIPE_MIX_LAST:
+        return fail(c, RV_ERR_INVALID, "RV_OPT_PIPE_MIX_LAST is read-only");
     case RV_OPT_BATCH_STREAMS:
         if (v != 1 && v != 2) return fail(c, RV_ERR_INVALID, "RV_OPT_BATCH_STREAMS: 1 or 2");
         c->batch_streams = (int)v;
@@ -243,6 +254,8 @@ rv_status rv_get_option(rv_ctx* c, int32_t opt, int64_t* v) {
     if (!c || !v) return RV_ERR_INVALID;
     switch (opt) {
     case RV_OPT_PIPE_ORDER: *v = c->pipe_order; return RV_OK;
+    case RV_OPT_PIPE_MIX: *v = (int64_t)c->pipe_mix; return RV_OK;
+    case RV_OPT_PIPE_MIX_LAST: *v = (int64_t)c->pipe_mix_last; return RV_OK;
     case RV_OPT_BATCH_STREAMS: *v = c->batch_streams; return RV_OK;
     case RV_OPT_FLOW_SPIN: *v = c->flow_spin; return RV_OK;
     case RV_OPT_FLOW_FORCE_FALLBACK: *v = c->flow_force_fallback ? 1 : 0; return RV_OK;
@@ -250,6 +263,23 @@ rv_status rv_get_option(rv_ctx* c, int32_t opt, int64_t* v) {
     case RV_OPT_GI_SHARD_PROBE: *v = c->gi_shard_probe ? 1 : 0; return RV_OK;
     default: return fail(c, RV_ERR_INVALID, "unknown option " + std::to_string(opt));
     }
+}
+
+rv_status rv_pipe_layout_map(int64_t order, int64_t mix, const uint32_t* lens, uint32_t first, uint32_t n,
+                             uint8_t* part, uint32_t* local) {
+    const uint32_t a = (uint32_t)(order >> 8 & 0xF), b = (uint32_t)(order >> 4 & 0xF), d = (uint32_t)(order & 0xF);
+    if (order < 0 || order > 0x210 || a > 2 || b > 2 || d > 2 || a == b || b == d || a == d) return RV_ERR_INVALID;
+    if (!lens || !part || !local || mix < 0 || (mix >> 24) > 0xFFFFFF || ((lens[0] | lens[1] | lens[2]) & 7u))
+        return RV_ERR_INVALID;
+    PipeParams p{};
+    pipe_dispatch(p, (uint32_t)order, (uint64_t)mix, lens);
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t j, l;
+        pipe_map(p.lay, first + i, j, l);
+        part[i] = (uint8_t)p.part[j];
+        local[i] = l;
+    }
+    return RV_OK;
 }
 
 // Frames in flight: frame k takes slot k % n; its stream first waits for

@@ -136,6 +136,12 @@ struct rv_ctx {
     int order_every = 4;          // frames between chunk re-orderings
     int pipe = 1;                 // rv_set_pipeline: pipelined reference frames
     uint32_t pipe_order = 0x102;  // RV_OPT_PIPE_ORDER: dispatch order, hex digits PIPE_* (first = high): pre-pass, GI, render
+    // RV_OPT_PIPE_MIX: k_ref_pipe's whole-frame dispatch pattern, head rows << 24 | pre-pass << 16 | GI << 8 |
+    // render rows per period (0: the three contiguous ranges); pipe_mix_last: what the last launch used.
+    // The default is for the throughput variant's launches (C4 -2.5 %, profiles/r07/pipe_mix_ab.txt); the
+    // latency variant's keep the contiguous order until the option is set (pipe_mix_set)
+    uint64_t pipe_mix = PIPE_MIX_DEFAULT, pipe_mix_last = 0;
+    bool pipe_mix_set = false;
     float* pipe_half[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [k & 1] {dist, shadow}
     bool gi_stats = false;        // rv_set_gi_stats
     // pipelined tile loop: packed tiles / rank-0 gather buffers per frame parity, GI shard staging

@@ -287,10 +287,9 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
         p.gi_pairs = (c->gi_pairs > 0 || (c->gi_pairs < 0 && tiles)) && pipe_latency_variant(f, rlen) ? 1u : 0u;
         const uint32_t lens[3] = {more ? pipe_len(f, PIPE_GI, p.gi_pairs ? 2 * mine : mine) : 0u,
                                   more ? pipe_len(f, PIPE_PP, 0) : 0u, rlen};
-        for (int i = 0; i < 3; i++) {
-            p.part[i] = (c->pipe_order >> (4 * (2 - i))) & 0xFu;
-            p.len[i] = lens[p.part[i]];
-        }
+        // the pattern is for whole frames (tile shares stay contiguous), and its default for the throughput variant
+        c->pipe_mix_last = tiles || (!c->pipe_mix_set && pipe_latency_variant(f, rlen)) ? 0 : c->pipe_mix;
+        pipe_dispatch(p, c->pipe_order, c->pipe_mix_last, lens);
         if (RV_PIPE_DIAG && getenv("RV_PIPE_WAVE_STATS") && more) {   // diagnostics: summarised by rv_destroy
             const uint32_t nb = p.len[0] + p.len[1] + p.len[2];
             if (!c->pipe_wstat) HIP_TRY(c, hipMalloc(&c->pipe_wstat, (size_t)PIPE_WSTAT_N * PIPE_WSTAT_MAXB * 4));
