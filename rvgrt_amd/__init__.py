@@ -11,7 +11,8 @@ from ._lib import (RV_F_GI, RV_F_PREPASS, RV_F_REF_FETCH, RV_F_SHADOW, RV_F_STAT
                    RV_WORLD_GI, RvError, RV_OPT_PIPE_ORDER, RV_OPT_BATCH_STREAMS, RV_OPT_FLOW_SPIN,
                    RV_OPT_FLOW_FORCE_FALLBACK, RV_OPT_GI_PAIRS, RV_OPT_GI_SHARD_PROBE, RV_OPT_PIPE_MIX,
                    RV_OPT_PIPE_MIX_LAST, RV_EXIT_SKY,
-                   RV_EXIT_COLUMN, RV_EXIT_SUN)
+                   RV_EXIT_COLUMN, RV_EXIT_SUN, RV_WORLD_COLTOP, RV_WORLD_HORIZON, RV_WORLD_DTOP,
+                   RV_TRACE_SKY, RV_TRACE_SUN, RV_TRACE_COL)
 from .configs import CONFIGS, RenderConfig
 from .render import Comm, LoopbackGroup, StateRender, camera_dict, camera_from_pose, edit_region, frame_desc, relight_box
 

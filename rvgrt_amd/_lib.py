@@ -18,6 +18,10 @@ RV_F_PREPASS, RV_F_WATER, RV_F_GI, RV_F_SHADOW, RV_F_STATS, RV_F_REF_FETCH = 1, 
 RV_FLAGS_REFERENCE = RV_F_PREPASS | RV_F_WATER | RV_F_GI
 RV_IMAGE_COLOR, RV_IMAGE_MOTION, RV_IMAGE_DEPTH, RV_IMAGE_HALF_DIST, RV_IMAGE_HALF_SHADOW = range(5)
 RV_WORLD_BITS, RV_WORLD_CSDF, RV_WORLD_GI = range(3)
+# test hooks (rv_world_export only): the exit tables as built on the device
+RV_WORLD_COLTOP, RV_WORLD_HORIZON, RV_WORLD_DTOP = 3, 4, 5
+# rv_trace_rays_variant: look-ahead group (1, 4, 8) | these bits
+RV_TRACE_SKY, RV_TRACE_SUN, RV_TRACE_COL = 0x100, 0x200, 0x400
 RV_PATH_FUSED, RV_PATH_WAVEFRONT = 0, 1
 # rv_set_option (include/rvgrt.h rv_option)
 RV_OPT_PIPE_ORDER, RV_OPT_BATCH_STREAMS, RV_OPT_FLOW_SPIN, RV_OPT_FLOW_FORCE_FALLBACK, RV_OPT_GI_PAIRS, \
@@ -133,6 +137,8 @@ SIGNATURES = [
     ("rv_image_ptr", I32, [P, I32, C.POINTER(P), C.POINTER(SZ)]),
     ("rv_readback", I32, [P, I32, P, SZ]),
     ("rv_trace_rays", I32, [P, P, P, P, I64, P]),
+    ("rv_trace_rays_variant", I32, [P, I32, P, P, P, I64, P]),
+    ("rv_world_top_info", I32, [P, C.POINTER(U32)]),
     ("rv_camera_from_pose", I32, [F, F, F, F, F, I32, I32, C.POINTER(rv_camera), P]),
     ("rv_stats_get", I32, [P, C.POINTER(rv_stats)]),
     ("rv_stats_stage", I32, [P, I32, C.POINTER(rv_stats)]),

@@ -630,9 +630,28 @@ rv_status rv_world_export(rv_ctx* c, int32_t kind, void* host, size_t bytes) {
         if (bytes != c->gi_bytes) return fail(c, RV_ERR_INVALID, "gi size mismatch");
         HIP_TRY(c, hipMemcpyAsync(host, c->gi, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (kind == RV_WORLD_COLTOP || kind == RV_WORLD_HORIZON || kind == RV_WORLD_DTOP) {
+        // the exit tables as world_top left them on the device (test hooks)
+        const size_t hzb = horizon_bytes(c->w.X, c->w.Z), dtb = dtop_bytes(c->w.X, c->w.Z);
+        if (bytes != (kind == RV_WORLD_DTOP ? dtb : hzb)) return fail(c, RV_ERR_INVALID, "exit table size mismatch");
+        const char* src = kind == RV_WORLD_COLTOP ? reinterpret_cast<const char*>(c->coltop)
+                        : reinterpret_cast<const char*>(c->brick) +
+                              (kind == RV_WORLD_HORIZON ? horizon_byte(c->w.coff) : dtop_byte(c->w.coff, c->w.X, c->w.Z));
+        if (!src) {   // RV_EXIT_SKY off (or no world yet): no column tops were built
+            std::memset(host, 0, bytes);
+            return RV_OK;
+        }
+        HIP_TRY(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else {
         return fail(c, RV_ERR_INVALID, "bad world kind");
     }
+    return RV_OK;
+}
+
+rv_status rv_world_top_info(rv_ctx* c, uint32_t* ytop) {
+    if (!c || !ytop) return RV_ERR_INVALID;
+    *ytop = c->w.ytop;
     return RV_OK;
 }
 
@@ -1274,9 +1293,9 @@ rv_status rv_readback(rv_ctx* c, int32_t kind, void* host, size_t pitch) {
     return RV_OK;
 }
 
-rv_status rv_trace_rays(rv_ctx* c, const float* org, const float* dir, const float* dist, int64_t n, rv_hit* out) {
-    if (!c || n < 0 || (n > 0 && (!org || !dir || !dist || !out))) return RV_ERR_INVALID;
-    if (n == 0) return RV_OK;
+// variant < 0: rv_trace_rays' kernel; else rv_trace_rays_variant's (validated by the caller)
+static rv_status trace_rays(rv_ctx* c, int32_t variant, const float* org, const float* dir, const float* dist,
+                            int64_t n, rv_hit* out) {
     float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
     RvHitDev* d_h = nullptr;
     HIP_TRY(c, hipMalloc(&d_o, (size_t)n * 12));
@@ -1287,14 +1306,39 @@ rv_status rv_trace_rays(rv_ctx* c, const float* org, const float* dir, const flo
     HIP_TRY(c, hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_t, dist, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     World tw = current_world(c);
-    tw.ytop = (uint32_t)tw.Y;   // rv_trace_rays reports the reference's step counts: no sky exit (and it
-                                // traces no sun rays through trace_sun)
-    launch_trace_rays(c->stream, tw, d_o, d_d, d_t, n, d_h);
+    if (variant < 0) {
+        tw.ytop = (uint32_t)tw.Y;   // rv_trace_rays reports the reference's step counts: no sky exit (and it
+                                    // traces no sun rays through trace_sun)
+        launch_trace_rays(c->stream, tw, d_o, d_d, d_t, n, d_h);
+    } else {
+        if (!(variant & RV_TRACE_SKY)) tw.ytop = (uint32_t)tw.Y;   // else the world's own sky exit, as the frames
+        launch_trace_rays_variant(c->stream, tw, variant & 0xFF, (variant & RV_TRACE_SUN) != 0,
+                                  (variant & RV_TRACE_COL) != 0, d_o, d_d, d_t, n, d_h);
+    }
     LAUNCH_CHECK(c);
     HIP_TRY(c, hipMemcpyAsync(out, d_h, (size_t)n * sizeof(RvHitDev), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     hipFree(d_o); hipFree(d_d); hipFree(d_t); hipFree(d_h);
     return RV_OK;
+}
+
+rv_status rv_trace_rays(rv_ctx* c, const float* org, const float* dir, const float* dist, int64_t n, rv_hit* out) {
+    if (!c || n < 0 || (n > 0 && (!org || !dir || !dist || !out))) return RV_ERR_INVALID;
+    if (n == 0) return RV_OK;
+    return trace_rays(c, -1, org, dir, dist, n, out);
+}
+
+rv_status rv_trace_rays_variant(rv_ctx* c, int32_t variant, const float* org, const float* dir, const float* dist,
+                                int64_t n, rv_hit* out) {
+    if (!c || n < 0 || (n > 0 && (!org || !dir || !dist || !out))) return RV_ERR_INVALID;
+    // the same list as launch_trace_rays_variant's: look-ahead 1, 4 or 8; COL on 4 or 8, never with SUN
+    const int g = variant & 0xFF;
+    const bool sun = (variant & RV_TRACE_SUN) != 0, col = (variant & RV_TRACE_COL) != 0;
+    if (variant < 0 || (variant & ~(0xFF | RV_TRACE_SKY | RV_TRACE_SUN | RV_TRACE_COL)) || (g != 1 && g != 4 && g != 8) ||
+        (col && (g == 1 || sun || !RV_DDA_REWALK)))
+        return fail(c, RV_ERR_INVALID, "rv_trace_rays_variant: unknown variant " + std::to_string(variant));
+    if (n == 0) return RV_OK;
+    return trace_rays(c, variant, org, dir, dist, n, out);
 }
 
 // Character::Update camera math (src/Character.cpp:18-126) for a static pose.

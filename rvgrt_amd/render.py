@@ -319,10 +319,20 @@ class StateRender:
             a = np.zeros(X * Y * Z // 32, np.uint32)
         elif kind == _lib.RV_WORLD_CSDF:
             a = np.zeros(X * Y * Z // 8, np.uint8)
+        elif kind in (_lib.RV_WORLD_COLTOP, _lib.RV_WORLD_HORIZON):   # test hooks: [z / 2, x / 2]
+            a = np.zeros((Z // 2, X // 2), np.uint32)
+        elif kind == _lib.RV_WORLD_DTOP:                              # [z / 8, x / 8]
+            a = np.zeros((Z // 8, X // 8), np.int32)
         else:
             a = np.zeros((X // 4) * (Y // 4) * (Z // 4) * 4, np.uint8)
         self._check(self._L.rv_world_export(self._h, kind, _ptr(a), a.nbytes), "rv_world_export")
         return a
+
+    def world_top_info(self) -> int:
+        """rv_world_top_info (test hook): the sky exit in effect, World::ytop."""
+        y = C.c_uint32()
+        self._check(self._L.rv_world_top_info(self._h, C.byref(y)), "rv_world_top_info")
+        return int(y.value)
 
     def world_edit(self, boxes):
         """rv_world_edit: set / clear voxel boxes (x0, y0, z0, x1, y1, z1, solid) in
@@ -450,18 +460,26 @@ class StateRender:
         return a
 
     # ------------------------------------------------------------ test surface
-    def trace_rays(self, org, dirs, dist) -> np.ndarray:
+    def trace_rays(self, org, dirs, dist, variant=None) -> np.ndarray:
+        """rv_trace_rays, or with `variant` (look-ahead group 1 / 4 / 8 | RV_TRACE_SKY / SUN / COL)
+        rv_trace_rays_variant: one of the frame kernels' traversals on the world's own exit
+        tables; `pad` then counts the look-ahead groups the ray's lane knew empty."""
         org = np.ascontiguousarray(org, np.float32)
         dirs = np.ascontiguousarray(dirs, np.float32)
         dist = np.ascontiguousarray(dist, np.float32)
         n = len(dist)
-        out = (rv_hit * max(n, 1))()
-        self._check(self._L.rv_trace_rays(self._h, _ptr(org), _ptr(dirs), _ptr(dist), n,
-                                          C.cast(out, C.c_void_p)), "rv_trace_rays")
         dt = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("u", "<f4"), ("v", "<f4"),
                        ("hit", "<i4"), ("undef", "<i4"), ("sphere_steps", "<i4"),
                        ("dda_steps", "<i4"), ("csdf_checks", "<i4"), ("pad", "<i4")])
-        return np.frombuffer(bytes(out), dt, count=n).copy()
+        assert dt.itemsize == C.sizeof(rv_hit)
+        out = np.zeros(max(n, 1), dt)
+        if variant is None:
+            self._check(self._L.rv_trace_rays(self._h, _ptr(org), _ptr(dirs), _ptr(dist), n, _ptr(out)),
+                        "rv_trace_rays")
+        else:
+            self._check(self._L.rv_trace_rays_variant(self._h, int(variant), _ptr(org), _ptr(dirs), _ptr(dist), n,
+                                                      _ptr(out)), "rv_trace_rays_variant")
+        return out[:n]
 
     def stats(self, stage=-1) -> dict:
         """Counters (RV_F_STATS frames) of one RV_STAGE_* (-1 = all stages)."""
