@@ -82,6 +82,8 @@ public:
     // Place / break blocks (no reference counterpart: its world is fixed after CArray::fill): voxel
     // boxes set or cleared in place, the CSDF and the early exits rebuilt around them (rv_world_edit)
     void editWorld(const rv_edit_box* boxes, int n) { check(rv_world_edit(ctx_, boxes, n), ctx_, "rv_world_edit"); }
+    // The world window moved by (dx, 0, dz) voxels over the generated terrain, in place (rv_world_scroll)
+    void scroll(int dx, int dz) { check(rv_world_scroll(ctx_, dx, dz), ctx_, "rv_world_scroll"); }
     // The GI cells of a box refreshed at once after an edit: `iterations` update steps with RNG frames
     // frame0, frame0 + 1, ... (rv_gi_relight; rv_gi_relight_box picks the box around the edit)
     void relightGI(const rv_gi_box& box, uint32_t frame0, int iterations, bool init = false) {

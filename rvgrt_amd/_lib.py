@@ -125,6 +125,12 @@ SIGNATURES = [
     ("rv_gi_relight", I32, [P, C.POINTER(rv_gi_box), U32, I32, I32]),
     ("rv_gi_relight_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("rv_gi_relight_box", I32, [I32, I32, I32, C.POINTER(rv_edit_box), I32, I32, C.POINTER(rv_gi_box)]),
+    ("rv_world_scroll", I32, [P, I32, I32]),
+    ("rv_world_scroll_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("rv_world_scroll_region", I32, [I32, I32, I32, I32, I32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_int32)]),
+    ("rv_scroll_view", I32, [I32, I32, C.POINTER(rv_camera), P, P]),
     ("rv_gi_update", I32, [P, U32, U64, U64]),
     ("rv_update_gi_data", I32, [P]),
     ("rv_draw_cuda", I32, [P, P, P, P, P, P, P, F, F]),

@@ -164,6 +164,7 @@ void rv_destroy(rv_ctx* c) {
     hipFree(c->coltop);
     hipFree(c->edit_boxes); hipFree(c->edit_flag); hipFree(c->edit_t0); hipFree(c->edit_t1);
     hipFree(c->relight_rec); hipFree(c->relight_dense[0]); hipFree(c->relight_dense[1]);
+    hipFree(c->scroll_tmp);
     hipFree(c->tiles.d); hipFree(c->untile_ids.d);
     hipFree(c->tilebuf);
     hipFree(c->hpos); hipFree(c->hinfo); hipFree(c->hsec); hipFree(c->pphit); hipFree(c->qcount);

@@ -19,6 +19,48 @@ bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n) {
     return true;
 }
 
+static CellBox grown(const int e0[3], const int e1[3], const int S[3], int gx, int gy, int gz) {
+    const int g[3] = {gx, gy, gz};
+    int a0[3], a1[3];
+    for (int a = 0; a < 3; a++) {
+        a0[a] = std::max(0, e0[a] - g[a]);
+        a1[a] = std::min(S[a], e1[a] + g[a]);
+    }
+    return CellBox{a0[0], a0[1], a0[2], a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]};
+}
+
+CsdfBoxes csdf_boxes(const int e0[3], const int e1[3], const int S[3]) {
+    CsdfBoxes b;
+    b.rf = grown(e0, e1, S, 64, 64, 64);
+    b.ry = grown(e0, e1, S, 64, 64, 128);
+    b.rx = grown(e0, e1, S, 64, 128, 128);
+    b.rs = grown(e0, e1, S, 128, 128, 128);
+    return b;
+}
+
+rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n) {
+    size_t n0 = 0, n1 = 0;
+    for (int i = 0; i < n; i++) {
+        n0 = std::max(n0, (size_t)b[i].rs.cells());
+        n1 = std::max(n1, (size_t)b[i].rx.cells());
+    }
+    if (rv_status s = dev_reserve(c, c->edit_t0, c->edit_t0_cap, n0)) return s;
+    if (rv_status s = dev_reserve(c, c->edit_t1, c->edit_t1_cap, n1)) return s;
+    for (int i = 0; i < n; i++)
+        launch_csdf_box(c->stream, c->brick, current_world(c), b[i].rs, b[i].rx, b[i].ry, b[i].rf, c->edit_t0,
+                        c->edit_t1);
+    LAUNCH_CHECK(c);
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    if (c->edit_t0_cap + c->edit_t1_cap > EDIT_SCRATCH_KEEP) {
+        hipFree(c->edit_t0);
+        hipFree(c->edit_t1);
+        c->edit_t0 = c->edit_t1 = nullptr;
+        c->edit_t0_cap = c->edit_t1_cap = 0;
+    }
+    HIP_TRY(c, se);
+    return RV_OK;
+}
+
 namespace {
 
 // What one rv_world_edit call touches.
@@ -39,20 +81,10 @@ namespace {
 // Everything outside F keeps its byte: it equals what a whole-grid build would write there.
 struct EditPlan {
     int lo[3], hi[3];        // voxel bounding box of the boxes, [lo, hi)
-    CellBox rs, rx, ry, rf;
+    CsdfBoxes b;
     uint64_t local_cells;    // cells the four local passes visit
     uint64_t full_cells;     // cells the four whole-grid passes visit
 };
-
-CellBox grown(const int e0[3], const int e1[3], const int S[3], int gx, int gy, int gz) {
-    const int g[3] = {gx, gy, gz};
-    int a0[3], a1[3];
-    for (int a = 0; a < 3; a++) {
-        a0[a] = std::max(0, e0[a] - g[a]);
-        a1[a] = std::min(S[a], e1[a] + g[a]);
-    }
-    return CellBox{a0[0], a0[1], a0[2], a1[0] - a0[0], a1[1] - a0[1], a1[2] - a0[2]};
-}
 
 // boxes validated, n >= 1
 EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
@@ -65,17 +97,11 @@ EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
     const int S[3] = {1 << (lx - 1), 1 << (ly - 1), 1 << (lz - 1)};
     int e0[3], e1[3];
     for (int a = 0; a < 3; a++) { e0[a] = p.lo[a] >> 1; e1[a] = ((p.hi[a] - 1) >> 1) + 1; }
-    p.rf = grown(e0, e1, S, 64, 64, 64);
-    p.ry = grown(e0, e1, S, 64, 64, 128);
-    p.rx = grown(e0, e1, S, 64, 128, 128);
-    p.rs = grown(e0, e1, S, 128, 128, 128);
-    p.local_cells = p.rs.cells() + p.rx.cells() + p.ry.cells() + p.rf.cells();
+    p.b = csdf_boxes(e0, e1, S);
+    p.local_cells = p.b.passes();
     p.full_cells = 4ull * (uint64_t)S[0] * (uint64_t)S[1] * (uint64_t)S[2];
     return p;
 }
-
-// Scratch of the local passes is kept between edits while it is small (a single block's is 26 MB).
-constexpr size_t EDIT_SCRATCH_KEEP = (size_t)64 << 20;
 
 }  // namespace
 
@@ -91,10 +117,10 @@ rv_status rv_world_edit_region(int32_t log2_x, int32_t log2_y, int32_t log2_z, c
         return RV_OK;
     }
     const EditPlan p = edit_plan(log2_x, log2_y, log2_z, boxes, n);
-    region[0] = p.rf.x0; region[1] = p.rf.x0 + p.rf.nx;
-    region[2] = p.rf.y0; region[3] = p.rf.y0 + p.rf.ny;
-    region[4] = p.rf.z0; region[5] = p.rf.z0 + p.rf.nz;
-    if (cells) *cells = p.rf.cells();
+    region[0] = p.b.rf.x0; region[1] = p.b.rf.x0 + p.b.rf.nx;
+    region[2] = p.b.rf.y0; region[3] = p.b.rf.y0 + p.b.rf.ny;
+    region[4] = p.b.rf.z0; region[5] = p.b.rf.z0 + p.b.rf.nz;
+    if (cells) *cells = p.b.rf.cells();
     return RV_OK;
 }
 
@@ -135,20 +161,9 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
         c->edit_cells = n_csdf(c);
         c->edit_full = 1;
     } else {
-        if (rv_status s = dev_reserve(c, c->edit_t0, c->edit_t0_cap, (size_t)p.rs.cells())) return s;
-        if (rv_status s = dev_reserve(c, c->edit_t1, c->edit_t1_cap, (size_t)p.rx.cells())) return s;
-        launch_csdf_box(c->stream, c->brick, current_world(c), p.rs, p.rx, p.ry, p.rf, c->edit_t0, c->edit_t1);
-        LAUNCH_CHECK(c);
-        const hipError_t se = hipStreamSynchronize(c->stream);
-        if (c->edit_t0_cap + c->edit_t1_cap > EDIT_SCRATCH_KEEP) {
-            hipFree(c->edit_t0);
-            hipFree(c->edit_t1);
-            c->edit_t0 = c->edit_t1 = nullptr;
-            c->edit_t0_cap = c->edit_t1_cap = 0;
-        }
-        HIP_TRY(c, se);
+        if (rv_status s = csdf_rebuild_boxes(c, &p.b, 1)) return s;
         if (rv_status ms = mark_world(c)) return ms;
-        c->edit_cells = p.rf.cells();
+        c->edit_cells = p.b.rf.cells();
     }
     c->edit_count++;
     return RV_OK;

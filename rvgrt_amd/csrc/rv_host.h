@@ -5,7 +5,8 @@
 //   rv_loops.cpp  the native frame loops (batched, pipelined, grouped), tile shards;
 //   rv_comm.cpp   the transport: RCCL resolved at run time, or the in-process loopback group;
 //   rv_edit.cpp   voxel edits in place (rv_world_edit);
-//   rv_relight.cpp  the GI refresh of a cell box (rv_gi_relight).
+//   rv_relight.cpp  the GI refresh of a cell box (rv_gi_relight);
+//   rv_scroll.cpp   the world window moved over the terrain (rv_world_scroll).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -234,6 +235,10 @@ struct rv_ctx {
     uint2* relight_rec = nullptr; size_t relight_rec_cap = 0;
     uint32_t* relight_dense[2] = {nullptr, nullptr}; size_t relight_dense_cap[2] = {0, 0};
     uint64_t relight_calls = 0, relight_cells = 0, relight_records = 0;
+    // rv_world_scroll: the scratch copy of the retained records (freed after a call when above the edit
+    // scratch's keep limit) and rv_world_scroll_info's record; the window's origin is cfg.seed_x / seed_z
+    void* scroll_tmp = nullptr; size_t scroll_tmp_cap = 0;
+    uint64_t scroll_count = 0, scroll_cells = 0; int scroll_full = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;
@@ -472,6 +477,20 @@ RV_HIDDEN rv_status tile_list(rv_ctx* c, const int32_t* tile_ids, int32_t ntiles
 // rv_edit.cpp: rv_create's limits on the world dims; a box list's validity in such a world
 RV_HIDDEN bool dims_ok(int lx, int ly, int lz);
 RV_HIDDEN bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n);
+// The nested boxes of a local CSDF rebuild (launch_csdf_box) around the coarse cells E = [e0, e1) whose
+// solidity may have changed, in a grid of S cells: rf = E grown by 64 per axis, and the inputs it needs
+// read backwards through the passes (rv_edit.cpp), each clipped to the grid; passes() = the cells the four
+// passes visit.  An empty E on an axis (e0 == e1, at a face) stands for cells that left the grid there.
+struct CsdfBoxes {
+    CellBox rs, rx, ry, rf;
+    uint64_t passes() const { return rs.cells() + rx.cells() + ry.cells() + rf.cells(); }
+};
+RV_HIDDEN CsdfBoxes csdf_boxes(const int e0[3], const int e1[3], const int S[3]);
+// Scratch of the local passes is kept between calls while it is small (a single block's is 26 MB).
+constexpr size_t EDIT_SCRATCH_KEEP = (size_t)64 << 20;
+// the passes over `n` sets of boxes, one after the other, through edit_t0 / edit_t1; waits for them, then
+// frees the scratch when it is above EDIT_SCRATCH_KEEP
+RV_HIDDEN rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n);
 
 // rv_comm.cpp: the four exchange operations of the loops and the bounded wait
 RV_HIDDEN double comm_timeout_s();

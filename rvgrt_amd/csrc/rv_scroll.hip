@@ -1,0 +1,137 @@
+// rv_scroll.hip -- gfx950 kernels of rv_world_scroll (include/rvgrt.h): the world window moved over the
+// terrain in place.  One step moves the window along one axis (x or z) by whole bricks:
+//   k_scroll_bricks  the bit record and the CSDF record of every retained brick to its new brick index,
+//   k_fill_box       the entering slab's voxels (k_fill_bricks' word body, fill_word),
+//   k_scroll_gi      the RGBA8 cell of every retained GI cell to its new index,
+//   k_scroll_gi_init the entering GI cells (k_gi_init's cell, gi_init_cell).
+// Both moves go through a dense scratch copy of what is retained (source and destination overlap, and no
+// order of concurrently running lanes makes an in-place move safe): one launch gathers the retained
+// records into the scratch, a second one writes them to their new places.  The CSDF of the slabs a step can
+// change is rebuilt by launch_csdf_box (rv_kernels.hip), the passes of rv_csdf_build.
+#include "../../include/rvgrt/rv_shade.h"
+
+namespace rv {
+
+// The retained records of a one-axis shift, as runs of contiguous bricks (bricks are ordered z fastest,
+// then y, then x: brick_of).  Retained brick r of the dense order sits at
+//   dst = (r / run) * row + r % run + dst0      after the shift, and came from      src = dst + delta.
+// x axis: one run (the retained x planes are contiguous), z axis: one run per (bx, by) row of NBZ bricks.
+struct BrickShift {
+    uint64_t nret;    // retained bricks
+    uint64_t run;     // contiguous retained bricks per row
+    uint64_t row;     // bricks between the starts of two rows
+    uint64_t dst0;    // first retained brick's new index
+    int64_t delta;    // old index - new index
+};
+
+// 16 B per lane: four lanes move one 64-B record, a wave 1 KiB of contiguous records.  Unit g: quarter g & 3
+// of dense record g >> 2; records [0, nret) are the bit records, [nret, 2 nret) the CSDF records (their own
+// region, coff bytes further on).  TO_SCRATCH: brick array (old index) -> scratch (dense); else scratch ->
+// brick array (new index).
+template <bool TO_SCRATCH>
+__global__ void __launch_bounds__(256) k_scroll_bricks(uint32_t* __restrict__ brick, uint4* __restrict__ scratch,
+                                                       BrickShift s, uint32_t coff) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (g >= s.nret * 8u) return;
+    const uint64_t rec = g >> 2;
+    const uint32_t q = (uint32_t)g & 3u;
+    const bool csdf = rec >= s.nret;
+    const uint64_t r = csdf ? rec - s.nret : rec;
+    const uint64_t dst = (r / s.run) * s.row + r % s.run + s.dst0;
+    const uint64_t b = TO_SCRATCH ? (uint64_t)((int64_t)dst + s.delta) : dst;
+    uint4* p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(brick) + (csdf ? (size_t)coff : 0) +
+                                        (b << BRICK_SHIFT)) + q;
+    if (TO_SCRATCH) scratch[g] = *p;
+    else *p = scratch[g];
+}
+
+// k_fill_bricks over the bricks of a box: one lane per bit word, word fastest, then the box's bricks z fastest.
+__global__ void __launch_bounds__(256) k_fill_box(uint32_t* __restrict__ brick, World w, CellBox b, int seed_x,
+                                                  int seed_z, uint64_t nwords) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (g >= nwords) return;
+    const uint32_t wd = (uint32_t)(g & 15u);
+    uint64_t t = g >> 4;
+    const uint32_t bz = (uint32_t)b.z0 + (uint32_t)(t % (uint64_t)b.nz);
+    t /= (uint64_t)b.nz;
+    const uint32_t by = (uint32_t)b.y0 + (uint32_t)(t % (uint64_t)b.ny), bx = (uint32_t)b.x0 + (uint32_t)(t / (uint64_t)b.ny);
+    brick[bits_word_index(brick_of(w, (int)bx, (int)by, (int)bz), wd)] = fill_word(bx, by, bz, wd, seed_x, seed_z);
+}
+
+// The GI cells of the box b (the retained cells at their new places), x fastest: cell d of the dense order
+// is (x, y, z), and held cell (x + sx, y, z + sz) before the shift.
+template <bool TO_SCRATCH>
+__global__ void __launch_bounds__(256) k_scroll_gi(uint32_t* __restrict__ gi, uint32_t* __restrict__ scratch, World w,
+                                                   CellBox b, int sx, int sz) {
+    const uint64_t d = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (d >= b.cells()) return;
+    int x, y, z;
+    b.cell(d, x, y, z);
+    if (TO_SCRATCH) scratch[d] = gi[gi_cell_index(w, x + sx, y, z + sz)];
+    else gi[gi_cell_index(w, x, y, z)] = scratch[d];
+}
+
+// k_gi_init's cell over the entering cells, straight into the grid (the trace reads the voxels only).
+__global__ void __launch_bounds__(256) k_scroll_gi_init(uint32_t* __restrict__ gi, World w, f3 sun, CellBox b,
+                                                        uint32_t lit, unsigned long long* counters) {
+    const uint64_t d = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const bool on = d < b.cells();
+    if (on) {
+        int x, y, z;
+        b.cell(d, x, y, z);
+        const uint32_t cell = gi_cell_index(w, x, y, z);
+        gi[cell] = gi_init_cell(w, sun, cell, lit);
+    }
+    const unsigned long long traced = __ballot(on);
+    if ((threadIdx.x & 63u) == 0 && traced) atomicAdd(&counters[CNT_GI_TRACES], (unsigned long long)__popcll(traced));
+}
+
+// ================================================================ launchers
+static inline uint32_t nblk(uint64_t n) { return (uint32_t)((n + 255) / 256); }
+
+void launch_scroll_bricks(hipStream_t s, uint32_t* brick, const World& w, int axis, int nb, void* scratch) {
+    const uint64_t NBX = (uint64_t)w.X >> 3, NBY = (uint64_t)w.Y >> 3, NBZ = (uint64_t)w.Z >> 3;
+    const uint64_t a = (uint64_t)(nb < 0 ? -nb : nb);   // bricks the window moves by; a < the axis' bricks
+    BrickShift sh;
+    if (axis == 0) {
+        const uint64_t plane = NBY * NBZ;   // = 1 << lbzy
+        sh.nret = (NBX - a) * plane;
+        sh.run = sh.nret;
+        sh.row = 0;
+        sh.dst0 = nb > 0 ? 0 : a * plane;
+        sh.delta = (int64_t)nb * (int64_t)plane;
+    } else {
+        sh.run = NBZ - a;
+        sh.row = NBZ;
+        sh.nret = NBX * NBY * sh.run;
+        sh.dst0 = nb > 0 ? 0 : a;
+        sh.delta = nb;
+    }
+    if (sh.nret == 0) return;
+    const dim3 grid(nblk(sh.nret * 8u)), wg(256);
+    hipLaunchKernelGGL(k_scroll_bricks<true>, grid, wg, 0, s, brick, static_cast<uint4*>(scratch), sh, w.coff);
+    hipLaunchKernelGGL(k_scroll_bricks<false>, grid, wg, 0, s, brick, static_cast<uint4*>(scratch), sh, w.coff);
+}
+
+void launch_fill_box(hipStream_t s, uint32_t* brick, const World& w, const CellBox& bricks, int sx, int sz) {
+    const uint64_t nwords = bricks.cells() * 16u;
+    if (nwords == 0) return;
+    hipLaunchKernelGGL(k_fill_box, dim3(nblk(nwords)), dim3(256), 0, s, brick, w, bricks, sx, sz, nwords);
+}
+
+void launch_scroll_gi(hipStream_t s, uint32_t* gi, const World& w, const CellBox& kept, int sx, int sz,
+                      void* scratch) {
+    if (kept.cells() == 0) return;
+    const dim3 grid(nblk(kept.cells())), wg(256);
+    hipLaunchKernelGGL(k_scroll_gi<true>, grid, wg, 0, s, gi, static_cast<uint32_t*>(scratch), w, kept, sx, sz);
+    hipLaunchKernelGGL(k_scroll_gi<false>, grid, wg, 0, s, gi, static_cast<uint32_t*>(scratch), w, kept, sx, sz);
+}
+
+void launch_scroll_gi_init(hipStream_t s, uint32_t* gi, const World& w, f3 sun, const CellBox& entering, uint32_t lit,
+                           unsigned long long* counters) {
+    if (entering.cells() == 0) return;
+    hipLaunchKernelGGL(k_scroll_gi_init, dim3(nblk(entering.cells())), dim3(256), 0, s, gi, w, sun, entering, lit,
+                       counters);
+}
+
+}  // namespace rv

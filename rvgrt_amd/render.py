@@ -93,6 +93,38 @@ def relight_box(log2_dims, boxes, margin=0):
     return (out.x0, out.y0, out.z0, out.x1, out.y1, out.z1)
 
 
+def scroll_region(log2_dims, axis, d):
+    """rv_world_scroll_region (host only): (trailing, leading, cells, full) for a
+    one-axis scroll by d voxels (axis 0 = x, 2 = z) of a world of these log2
+    dims -- the two coarse-cell boxes (cx0, cx1, cy0, cy1, cz0, cz1) whose CSDF
+    bytes world_scroll recomputes, their volume, and whether it runs the
+    whole-grid build instead (then trailing is the whole grid, leading empty)."""
+    L = _lib.load()
+    region = (C.c_int32 * 12)()
+    cells, full = C.c_uint64(), C.c_int32()
+    st = L.rv_world_scroll_region(int(log2_dims[0]), int(log2_dims[1]), int(log2_dims[2]), int(axis), int(d),
+                                  region, C.byref(cells), C.byref(full))
+    if st != 0:
+        raise RvError(f"rv_world_scroll_region: {_lib.STATUS_NAMES.get(st, st)}")
+    return tuple(region[:6]), tuple(region[6:]), int(cells.value), bool(full.value)
+
+
+def scroll_view(dx, dz, cam: rv_camera = None, vp=None, prev_vp=None):
+    """rv_scroll_view (host only): (cam, vp, prev_vp) re-expressed in the grid after
+    world_scroll(dx, dz) -- copies; the arguments are left alone, None stays None."""
+    L = _lib.load()
+    c2 = None
+    if cam is not None:
+        c2 = rv_camera()
+        C.memmove(C.byref(c2), C.byref(cam), C.sizeof(rv_camera))
+    m = [None if a is None else np.array(a, np.float32).reshape(16) for a in (vp, prev_vp)]
+    st = L.rv_scroll_view(int(dx), int(dz), None if c2 is None else C.byref(c2),
+                          *[None if a is None else _ptr(a) for a in m])
+    if st != 0:
+        raise RvError(f"rv_scroll_view: {_lib.STATUS_NAMES.get(st, st)}")
+    return c2, m[0], m[1]
+
+
 def rccl_path():
     """The RCCL of the HIP runtime this process uses: torch's bundled librccl
     when torch is already imported (the library then shares torch's runtime),
@@ -347,6 +379,23 @@ class StateRender:
         e, n, f = C.c_uint64(), C.c_uint64(), C.c_int32()
         self._check(self._L.rv_world_edit_info(self._h, C.byref(e), C.byref(n), C.byref(f)), "rv_world_edit_info")
         return int(e.value), int(n.value), bool(f.value)
+
+    def world_scroll(self, dx, dz):
+        """rv_world_scroll: the window moves by (dx, 0, dz) voxels (multiples of 8) over
+        the generated terrain; retained voxels, CSDF bytes and GI cells move to their
+        new index, the entering slab is generated at the new origin, the CSDF slabs
+        the move can change and the exits are rebuilt, entering GI cells take
+        gi_init's value.  Synchronous."""
+        self._check(self._L.rv_world_scroll(self._h, int(dx), int(dz)), "rv_world_scroll")
+
+    def world_scroll_info(self):
+        """(scrolls, csdf_cells, last_full, (origin_x, origin_z)): calls that moved the
+        window, the coarse cells the last one recomputed, whether a step of it ran
+        the whole-grid build, the window's origin."""
+        n, c, f, ox, oz = C.c_uint64(), C.c_uint64(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._L.rv_world_scroll_info(self._h, C.byref(n), C.byref(c), C.byref(f), C.byref(ox),
+                                                 C.byref(oz)), "rv_world_scroll_info")
+        return int(n.value), int(c.value), bool(f.value), (int(ox.value), int(oz.value))
 
     def gi_relight(self, box, frame0, iterations, init=False):
         """rv_gi_relight: `iterations` update steps (RNG frames frame0, frame0 + 1, ...)
