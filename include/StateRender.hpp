@@ -84,6 +84,16 @@ public:
     void editWorld(const rv_edit_box* boxes, int n) { check(rv_world_edit(ctx_, boxes, n), ctx_, "rv_world_edit"); }
     // The world window moved by (dx, 0, dz) voxels over the generated terrain, in place (rv_world_scroll)
     void scroll(int dx, int dz) { check(rv_world_scroll(ctx_, dx, dz), ctx_, "rv_world_scroll"); }
+    // The texture origin (rv_texture_origin_set) and whether scroll() moves it with the window
+    // (rv_texture_follow_scroll): setTextureOrigin(seed_x, seed_z) once, then textureFollowScroll(true), anchors the
+    // block textures to the terrain
+    void setTextureOrigin(int ox, int oz) { check(rv_texture_origin_set(ctx_, ox, oz), ctx_, "rv_texture_origin_set"); }
+    void textureFollowScroll(bool on) { check(rv_texture_follow_scroll(ctx_, on ? 1 : 0), ctx_, "rv_texture_follow_scroll"); }
+    void textureOrigin(int& ox, int& oz, bool& follow) const {
+        int32_t x = 0, z = 0, f = 0;
+        check(rv_texture_origin_get(ctx_, &x, &z, &f), ctx_, "rv_texture_origin_get");
+        ox = x; oz = z; follow = f != 0;
+    }
     // The GI cells of a box refreshed at once after an edit: `iterations` update steps with RNG frames
     // frame0, frame0 + 1, ... (rv_gi_relight; rv_gi_relight_box picks the box around the edit)
     void relightGI(const rv_gi_box& box, uint32_t frame0, int iterations, bool init = false) {

@@ -131,6 +131,11 @@ SIGNATURES = [
     ("rv_world_scroll_region", I32, [I32, I32, I32, I32, I32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_int32)]),
     ("rv_scroll_view", I32, [I32, I32, C.POINTER(rv_camera), P, P]),
+    ("rv_texture_origin_set", I32, [P, I32, I32]),
+    ("rv_texture_follow_scroll", I32, [P, I32]),
+    ("rv_texture_origin_get", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("rv_texture_tiles", I32, [P, P, I64, P]),
+    ("rv_texture_tile_at", I32, [I32, I32, P, I64, P]),
     ("rv_gi_update", I32, [P, U32, U64, U64]),
     ("rv_update_gi_data", I32, [P]),
     ("rv_draw_cuda", I32, [P, P, P, P, P, P, P, F, F]),

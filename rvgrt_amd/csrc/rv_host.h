@@ -239,6 +239,7 @@ struct rv_ctx {
     // scratch's keep limit) and rv_world_scroll_info's record; the window's origin is cfg.seed_x / seed_z
     void* scroll_tmp = nullptr; size_t scroll_tmp_cap = 0;
     uint64_t scroll_count = 0, scroll_cells = 0; int scroll_full = 0;
+    bool tex_follow = false;       // rv_texture_follow_scroll: a scroll adds its step to w.tex_ox / tex_oz
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;

@@ -1,7 +1,9 @@
 // rv_scroll.cpp -- host side of librvgrt_hip.so, part 6 of the C ABI (include/rvgrt.h): the world window
 // moved over the generated terrain in place (rv_world_scroll, rv_world_scroll_info), the host-only plan of
 // the CSDF cells a one-axis step rebuilds (rv_world_scroll_region) and the camera / VP matrices re-expressed
-// in the moved grid (rv_scroll_view).  The kernels are in rv_scroll.hip.
+// in the moved grid (rv_scroll_view), and the texture origin that can follow the window (rv_texture_origin_set,
+// rv_texture_follow_scroll, rv_texture_origin_get, the test hooks rv_texture_tiles and rv_texture_tile_at).
+// The kernels are in rv_scroll.hip.
 #include "rv_host.h"
 
 namespace {
@@ -71,6 +73,12 @@ void box_out(const CellBox& b, int32_t r[6]) {
 bool origin_ok(int64_t o, int64_t d, int64_t dim) {
     return o + d >= INT32_MIN && o + d + dim <= INT32_MAX;
 }
+// A texture origin (o + d along an axis of dim voxels) whose every lattice point fits an int: the second
+// point of sampleTexture lies up to `reach` (1322 along x, 722 along z: the offset + the carry) further on
+bool tex_origin_ok(int64_t o, int64_t d, int64_t dim, int64_t reach) {
+    return o + d >= INT32_MIN && o + d + dim + reach <= INT32_MAX;
+}
+constexpr int64_t TEX_REACH_X = 1322, TEX_REACH_Z = 722;
 
 // One step: the window moves by d voxels along `axis` (validated: a multiple of 8, not 0, no overflow).
 rv_status scroll_axis(rv_ctx* c, int axis, int d, uint64_t* cells, int* full) {
@@ -119,6 +127,21 @@ rv_status scroll_axis(rv_ctx* c, int axis, int d, uint64_t* cells, int* full) {
                           c->cfg.gi_init_saturate ? RV_GI_LIT_SATURATE : RV_GI_LIT_REFERENCE,
                           c->counters + ST_GI * NCNT);
     LAUNCH_CHECK(c);
+    // the texture origin follows the window: the retained table entries to their new index, the entering
+    // ones at the new origin (rows below tex_ny, which a scroll keeps); without a table only the origin moves
+    if (c->tex_follow) {
+        (axis == 0 ? c->w.tex_ox : c->w.tex_oz) += d;
+        if (c->tex) {
+            if (p.all) {
+                launch_tex_table(c->stream, c->tex, c->w);
+            } else {
+                launch_scroll_tex(c->stream, c->tex, c->w, axis, nb);
+                slab.ny = (int)(w.tex_ny >> 3);
+                launch_tex_box(c->stream, c->tex, c->w, slab);
+            }
+            LAUNCH_CHECK(c);
+        }
+    }
     if (rv_status ms = mark_world(c)) return ms;
     *cells += p.cells;
     *full |= p.full ? 1 : 0;
@@ -153,6 +176,9 @@ rv_status rv_world_scroll(rv_ctx* c, int32_t dx, int32_t dz) {
     if (dx % 8 != 0 || dz % 8 != 0) return fail(c, RV_ERR_INVALID, "rv_world_scroll: dx, dz must be multiples of 8");
     if (!origin_ok(c->cfg.seed_x, dx, c->w.X) || !origin_ok(c->cfg.seed_z, dz, c->w.Z))
         return fail(c, RV_ERR_INVALID, "rv_world_scroll: the window's origin would leave the int32 range");
+    if (c->tex_follow && (!tex_origin_ok(c->w.tex_ox, dx, c->w.X, TEX_REACH_X) ||
+                          !tex_origin_ok(c->w.tex_oz, dz, c->w.Z, TEX_REACH_Z)))
+        return fail(c, RV_ERR_INVALID, "rv_world_scroll: the texture origin would leave the int32 range");
     if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_world_scroll before a world build or import");
     if (dx == 0 && dz == 0) return RV_OK;
     if (rv_status ws = wait_all_frames(c)) return ws;
@@ -186,6 +212,78 @@ rv_status rv_world_scroll_info(rv_ctx* c, uint64_t* scrolls, uint64_t* csdf_cell
     if (last_full) *last_full = c->scroll_full;
     if (origin_x) *origin_x = c->cfg.seed_x;
     if (origin_z) *origin_z = c->cfg.seed_z;
+    return RV_OK;
+}
+
+rv_status rv_texture_origin_set(rv_ctx* c, int32_t ox, int32_t oz) {
+    if (!c) return RV_ERR_INVALID;
+    if (!tex_origin_ok(ox, 0, c->w.X, TEX_REACH_X) || !tex_origin_ok(oz, 0, c->w.Z, TEX_REACH_Z))
+        return fail(c, RV_ERR_INVALID, "rv_texture_origin_set: a lattice point would leave the int32 range");
+    if (ox == c->w.tex_ox && oz == c->w.tex_oz) return RV_OK;
+    if (rv_status ws = wait_all_frames(c)) return ws;
+    // work computed ahead sampled the old textures (the GI update multiplies a bounce hit's colour by them)
+    c->spec_gi = false;
+    c->carry_gi = c->carry_pp = false;
+    c->w.tex_ox = ox;
+    c->w.tex_oz = oz;
+    if (c->tex) {   // (not built yet: tex_table builds it at this origin)
+        launch_tex_table(c->stream, c->tex, c->w);
+        LAUNCH_CHECK(c);
+    }
+    if (rv_status ms = mark_world(c)) return ms;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RV_OK;
+}
+
+rv_status rv_texture_follow_scroll(rv_ctx* c, int32_t on) {
+    if (!c) return RV_ERR_INVALID;
+    c->tex_follow = on != 0;
+    return RV_OK;
+}
+
+rv_status rv_texture_origin_get(rv_ctx* c, int32_t* ox, int32_t* oz, int32_t* follow) {
+    if (!c) return RV_ERR_INVALID;
+    if (ox) *ox = c->w.tex_ox;
+    if (oz) *oz = c->w.tex_oz;
+    if (follow) *follow = c->tex_follow ? 1 : 0;
+    return RV_OK;
+}
+
+rv_status rv_texture_tiles(rv_ctx* c, const float* pos, int64_t n, uint8_t* tiles) {
+    if (!c || n < 0 || (n > 0 && (!pos || !tiles))) return RV_ERR_INVALID;
+    if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_texture_tiles before a world build or import");
+    if (n == 0) return RV_OK;
+    if (rv_status ws = wait_all_frames(c)) return ws;
+    float* dp = nullptr;
+    uint8_t* dt = nullptr;
+    HIP_TRY(c, hipMalloc((void**)&dp, (size_t)n * 12));
+    if (hipMalloc((void**)&dt, (size_t)n) != hipSuccess) {
+        hipFree(dp);
+        return fail(c, RV_ERR_OOM, "rv_texture_tiles: out of device memory");
+    }
+    hipError_t e = hipMemcpyAsync(dp, pos, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_texture_tiles(c->stream, current_world(c), dp, n, dt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(tiles, dt, (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    hipFree(dp);
+    hipFree(dt);
+    HIP_TRY(c, e);
+    HIP_TRY(c, se);
+    return RV_OK;
+}
+
+rv_status rv_texture_tile_at(int32_t ox, int32_t oz, const float* pos, int64_t n, uint8_t* tiles) {
+    if (n < 0 || (n > 0 && (!pos || !tiles)) || !tex_origin_ok(ox, 0, 0, TEX_REACH_X) ||
+        !tex_origin_ok(oz, 0, 0, TEX_REACH_Z))
+        return RV_ERR_INVALID;
+    World w{};   // no table: the noise, as a frame kernel evaluates it outside the table
+    w.tex_ox = ox;
+    w.tex_oz = oz;
+    for (int64_t i = 0; i < n; i++)
+        tiles[i] = (uint8_t)texture_tile(w, host_v(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]));
     return RV_OK;
 }
 

@@ -125,6 +125,19 @@ def scroll_view(dx, dz, cam: rv_camera = None, vp=None, prev_vp=None):
     return c2, m[0], m[1]
 
 
+def texture_tile_at(ox, oz, pos):
+    """rv_texture_tile_at (host only): sampleTexture's atlas tile, a uint8 0xYX per
+    position (n, 3) float32, evaluated on the CPU from the noise at texture origin
+    (ox, oz) -- the function the kernels call."""
+    L = _lib.load()
+    p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    out = np.zeros(len(p), np.uint8)
+    st = L.rv_texture_tile_at(int(ox), int(oz), _ptr(p), len(p), _ptr(out))
+    if st != 0:
+        raise RvError(f"rv_texture_tile_at: {_lib.STATUS_NAMES.get(st, st)}")
+    return out
+
+
 def rccl_path():
     """The RCCL of the HIP runtime this process uses: torch's bundled librccl
     when torch is already imported (the library then shares torch's runtime),
@@ -396,6 +409,32 @@ class StateRender:
         self._check(self._L.rv_world_scroll_info(self._h, C.byref(n), C.byref(c), C.byref(f), C.byref(ox),
                                                  C.byref(oz)), "rv_world_scroll_info")
         return int(n.value), int(c.value), bool(f.value), (int(ox.value), int(oz.value))
+
+    def texture_origin_set(self, ox, oz):
+        """rv_texture_origin_set: sampleTexture's lattice points are shifted by (ox, 0, oz)
+        as integers; the tile table is rebuilt at the new origin.  Synchronous; discards
+        work computed ahead (unless the origin is the one the context has)."""
+        self._check(self._L.rv_texture_origin_set(self._h, int(ox), int(oz)), "rv_texture_origin_set")
+
+    def texture_follow_scroll(self, on):
+        """rv_texture_follow_scroll: world_scroll(dx, dz) also adds (dx, dz) to the texture
+        origin, so the textures stay anchored to the terrain."""
+        self._check(self._L.rv_texture_follow_scroll(self._h, int(bool(on))), "rv_texture_follow_scroll")
+
+    def texture_origin(self):
+        """((ox, oz), follow): the texture origin and whether it follows scrolls."""
+        ox, oz, f = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._L.rv_texture_origin_get(self._h, C.byref(ox), C.byref(oz), C.byref(f)),
+                    "rv_texture_origin_get")
+        return (int(ox.value), int(oz.value)), bool(f.value)
+
+    def texture_tiles(self, pos):
+        """rv_texture_tiles (test hook): the kernels' atlas tile, a uint8 0xYX per position
+        (n, 3) float32, against this context's tile table and texture origin."""
+        p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        out = np.zeros(len(p), np.uint8)
+        self._check(self._L.rv_texture_tiles(self._h, _ptr(p), len(p), _ptr(out)), "rv_texture_tiles")
+        return out
 
     def gi_relight(self, box, frame0, iterations, init=False):
         """rv_gi_relight: `iterations` update steps (RNG frames frame0, frame0 + 1, ...)
