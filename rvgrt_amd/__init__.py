@@ -14,9 +14,9 @@ from ._lib import (RV_F_GI, RV_F_PREPASS, RV_F_REF_FETCH, RV_F_SHADOW, RV_F_STAT
                    RV_EXIT_COLUMN, RV_EXIT_SUN, RV_WORLD_COLTOP, RV_WORLD_HORIZON, RV_WORLD_DTOP,
                    RV_TRACE_SKY, RV_TRACE_SUN, RV_TRACE_COL)
 from .configs import CONFIGS, RenderConfig
-from .render import Comm, LoopbackGroup, StateRender, camera_dict, camera_from_pose, edit_region, frame_desc, relight_box, scroll_region, scroll_view, texture_tile_at
+from .render import Comm, LoopbackGroup, StateRender, camera_dict, camera_from_pose, edit_region, frame_desc, relight_box, scroll_region, scroll_view, texture_tile_at, persist_column_map
 
-__all__ = ["StateRender", "Comm", "LoopbackGroup", "camera_from_pose", "camera_dict", "frame_desc", "edit_region", "relight_box", "scroll_region", "scroll_view", "texture_tile_at", "CONFIGS", "RenderConfig", "RvError",
+__all__ = ["StateRender", "Comm", "LoopbackGroup", "camera_from_pose", "camera_dict", "frame_desc", "edit_region", "relight_box", "scroll_region", "scroll_view", "texture_tile_at", "persist_column_map", "CONFIGS", "RenderConfig", "RvError",
            "RV_F_GI", "RV_F_PREPASS", "RV_F_REF_FETCH", "RV_F_SHADOW", "RV_F_STATS", "RV_F_WATER",
            "RV_FLAGS_REFERENCE", "RV_IMAGE_COLOR", "RV_IMAGE_DEPTH", "RV_IMAGE_HALF_DIST",
            "RV_IMAGE_HALF_SHADOW", "RV_IMAGE_MOTION", "RV_WORLD_BITS", "RV_WORLD_CSDF",

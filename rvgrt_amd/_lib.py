@@ -131,6 +131,16 @@ SIGNATURES = [
     ("rv_world_scroll_region", I32, [I32, I32, I32, I32, I32, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_int32)]),
     ("rv_scroll_view", I32, [I32, I32, C.POINTER(rv_camera), P, P]),
+    ("rv_world_persist", I32, [P, I32]),
+    ("rv_world_persist_info", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rv_world_persist_flush", I32, [P]),
+    ("rv_world_store_list", I32, [P, P, I64, C.POINTER(C.c_int64)]),
+    ("rv_world_store_get", I32, [P, I32, I32, P, SZ]),
+    ("rv_world_store_put", I32, [P, I32, I32, P, SZ]),
+    ("rv_world_store_clear", I32, [P]),
+    ("rv_world_columns_read", I32, [P, P, I32, P, SZ]),
+    ("rv_persist_column_map", I32, [I32, I32, I32, I32, I32, P]),
     ("rv_texture_origin_set", I32, [P, I32, I32]),
     ("rv_texture_follow_scroll", I32, [P, I32]),
     ("rv_texture_origin_get", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -165,6 +165,8 @@ void rv_destroy(rv_ctx* c) {
     hipFree(c->edit_boxes); hipFree(c->edit_flag); hipFree(c->edit_t0); hipFree(c->edit_t1);
     hipFree(c->relight_rec); hipFree(c->relight_dense[0]); hipFree(c->relight_dense[1]);
     hipFree(c->scroll_tmp);
+    hipFree(c->persist_cols); hipFree(c->persist_stage);
+    if (c->persist_stage_h) hipHostFree(c->persist_stage_h);
     hipFree(c->tiles.d); hipFree(c->untile_ids.d);
     hipFree(c->tilebuf);
     hipFree(c->hpos); hipFree(c->hinfo); hipFree(c->hsec); hipFree(c->pphit); hipFree(c->qcount);
@@ -559,9 +561,18 @@ rv_status rv_gi_init(rv_ctx* c) {
 rv_status rv_world_build(rv_ctx* c) {
     if (!c) return RV_ERR_INVALID;
     if (rv_status ws = wait_all_frames(c)) return ws;
+    // persistence: every column is generated anew, so no column stays dirty, and the stored ones among them
+    // take their saved bits before anything is derived from the bits
+    const ColumnRange all{0, c->w.X >> 3, 0, c->w.Z >> 3};
+    if (c->persist) {
+        c->persist_dirty.clear();
+        if (rv_status s = persist_reserve(c, persist_stored_in(c, all, c->cfg.seed_x, c->cfg.seed_z))) return s;
+    }
     c->geom_ver++;
     launch_fill_bricks(c->stream, c->brick, current_world(c), c->cfg.seed_x, c->cfg.seed_z);
     LAUNCH_CHECK(c);
+    if (rv_status s = persist_restore(c, all)) return s;
+    persist_trim(c);
     if (rv_status ts = world_top(c)) return ts;
     if (rv_status ts = tex_table(c)) return ts;
     rv_status s = rv_csdf_build(c);
@@ -585,6 +596,7 @@ rv_status rv_world_import(rv_ctx* c, int32_t kind, const void* host, size_t byte
         LAUNCH_CHECK(c);
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         hipFree(d);
+        persist_mark(c, ColumnRange{0, c->w.X >> 3, 0, c->w.Z >> 3});   // persistence: none of it is the generator's
         if (rv_status ts = world_top(c)) return ts;
         if (rv_status ts = tex_table(c)) return ts;
     } else if (kind == RV_WORLD_CSDF) {

@@ -154,6 +154,9 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
     c->edit_full = 0;
     if (!changed) return RV_OK;   // every voxel already had its value: nothing to rebuild or invalidate
 
+    for (int i = 0; i < n; i++)   // persistence: the columns under each box may now differ from the generator's
+        persist_mark(c, ColumnRange{boxes[i].x0 >> 3, ((boxes[i].x1 - 1) >> 3) + 1, boxes[i].z0 >> 3,
+                                    ((boxes[i].z1 - 1) >> 3) + 1});
     c->geom_ver++;
     if (rv_status ts = world_top(c)) return ts;   // the exits, from the bits (a cleared voxel can lower them)
     if (p.local_cells >= p.full_cells) {

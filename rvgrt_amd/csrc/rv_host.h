@@ -6,7 +6,8 @@
 //   rv_comm.cpp   the transport: RCCL resolved at run time, or the in-process loopback group;
 //   rv_edit.cpp   voxel edits in place (rv_world_edit);
 //   rv_relight.cpp  the GI refresh of a cell box (rv_gi_relight);
-//   rv_scroll.cpp   the world window moved over the terrain (rv_world_scroll).
+//   rv_scroll.cpp   the world window moved over the terrain (rv_world_scroll);
+//   rv_persist.cpp  edited columns kept across scrolls (rv_world_persist).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -15,7 +16,9 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <tuple>
 #include <cmath>
@@ -240,6 +243,20 @@ struct rv_ctx {
     void* scroll_tmp = nullptr; size_t scroll_tmp_cap = 0;
     uint64_t scroll_count = 0, scroll_cells = 0; int scroll_full = 0;
     bool tex_follow = false;       // rv_texture_follow_scroll: a scroll adds its step to w.tex_ox / tex_oz
+    // rv_world_persist (rv_persist.cpp).  A column's key is (wz, wx), the terrain coordinate of its low corner,
+    // so both containers iterate in rv_world_store_list's order.  dirty: columns of the window whose bits may
+    // differ from the generator's; store: saved column bits (2 Y words), used the next time the library
+    // generates the column.  The device list of columns and the staging buffer of their bits, the host copies
+    // they are filled from or read into (both staging buffers freed after a call when above the edit scratch's
+    // keep limit), and rv_world_persist_info's totals.
+    bool persist = false;
+    std::set<std::pair<int32_t, int32_t>> persist_dirty;
+    std::map<std::pair<int32_t, int32_t>, std::vector<uint32_t>> persist_store;
+    int2* persist_cols = nullptr; size_t persist_cols_cap = 0;
+    uint32_t* persist_stage = nullptr; size_t persist_stage_cap = 0;
+    std::vector<int2> persist_cols_h;
+    uint32_t* persist_stage_h = nullptr; size_t persist_stage_h_cap = 0;   // pinned: the two 1-MiB copies of a C4 step
+    uint64_t persist_captured = 0, persist_restored = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;
@@ -492,6 +509,24 @@ constexpr size_t EDIT_SCRATCH_KEEP = (size_t)64 << 20;
 // the passes over `n` sets of boxes, one after the other, through edit_t0 / edit_t1; waits for them, then
 // frees the scratch when it is above EDIT_SCRATCH_KEEP
 RV_HIDDEN rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n);
+
+// rv_persist.cpp: the marking, capturing and restoring that rv_world_edit, rv_world_import, rv_world_build
+// and rv_world_scroll do while persistence is on (every one returns at once while it is off).  A range is
+// the brick columns [bx0, bx1) x [bz0, bz1) of the window; keys are taken at the origin (ox, oz).
+struct ColumnRange { int bx0, bx1, bz0, bz1; };
+RV_HIDDEN void persist_mark(rv_ctx* c, const ColumnRange& r);
+// how many columns of r are dirty / have an entry in the store when the window's origin is (ox, oz)
+RV_HIDDEN size_t persist_dirty_in(const rv_ctx* c, const ColumnRange& r, int32_t ox, int32_t oz);
+RV_HIDDEN size_t persist_stored_in(const rv_ctx* c, const ColumnRange& r, int32_t ox, int32_t oz);
+// the device list and staging buffer for n columns; before anything is written, like scroll_tmp
+RV_HIDDEN rv_status persist_reserve(rv_ctx* c, size_t ncols);
+// the dirty columns of r: gathered, copied to the host (waits for the stream), put into the store (a newer
+// copy replaces an entry) and, unless keep_dirty, taken out of the dirty set.  Nothing dirty: no launch, copy or wait
+RV_HIDDEN rv_status persist_capture(rv_ctx* c, const ColumnRange& r, bool keep_dirty);
+// the stored columns of r, at the context's current origin: scattered over the freshly generated bits (waits
+// for the stream), taken out of the store and marked dirty.  Nothing stored: no launch, copy or wait
+RV_HIDDEN rv_status persist_restore(rv_ctx* c, const ColumnRange& r);
+RV_HIDDEN void persist_trim(rv_ctx* c);   // frees the device buffers when above EDIT_SCRATCH_KEEP
 
 // rv_comm.cpp: the four exchange operations of the loops and the bounded wait
 RV_HIDDEN double comm_timeout_s();

@@ -92,8 +92,22 @@ rv_status scroll_axis(rv_ctx* c, int axis, int d, uint64_t* cells, int* full) {
     // before anything is written: a failed allocation leaves the world as it was
     const size_t kept = (size_t)(NB - ab) * (size_t)(axis == 0 ? NBZ : NBX) * (size_t)NBY;
     if (rv_status s = dev_reserve(c, c->scroll_tmp, c->scroll_tmp_cap, kept * 128)) return s;
+    // persistence: the brick columns that leave (old window) and those that enter (new window), and the
+    // staging for the dirty ones among the former and the stored ones among the latter, reserved here too
+    ColumnRange col_leave{0, NBX, 0, NBZ}, col_enter = col_leave;
+    (axis == 0 ? col_leave.bx0 : col_leave.bz0) = d > 0 ? 0 : NB - ab;
+    (axis == 0 ? col_leave.bx1 : col_leave.bz1) = d > 0 ? ab : NB;
+    (axis == 0 ? col_enter.bx0 : col_enter.bz0) = d > 0 ? NB - ab : 0;
+    (axis == 0 ? col_enter.bx1 : col_enter.bz1) = d > 0 ? NB : ab;
+    if (c->persist) {
+        const int32_t ox = c->cfg.seed_x, oz = c->cfg.seed_z;
+        const size_t nl = persist_dirty_in(c, col_leave, ox, oz);
+        const size_t ne = persist_stored_in(c, col_enter, ox + (axis == 0 ? d : 0), oz + (axis == 2 ? d : 0));
+        if (rv_status s = persist_reserve(c, std::max(nl, ne))) return s;
+    }
 
     c->geom_ver++;
+    if (rv_status s = persist_capture(c, col_leave, false)) return s;   // before the retained bricks move
     if (!p.all) {
         launch_scroll_bricks(c->stream, c->brick, current_world(c), axis, nb, c->scroll_tmp);
         LAUNCH_CHECK(c);
@@ -105,6 +119,9 @@ rv_status scroll_axis(rv_ctx* c, int axis, int d, uint64_t* cells, int* full) {
     if (d > 0) (axis == 0 ? slab.x0 : slab.z0) = NB - ab;
     launch_fill_box(c->stream, c->brick, current_world(c), slab, c->cfg.seed_x, c->cfg.seed_z);
     LAUNCH_CHECK(c);
+    // persistence: the stored columns of the slab take their saved bits; the exits, the CSDF slabs, the
+    // entering GI cells and the tile table below all see the final bits
+    if (rv_status s = persist_restore(c, col_enter)) return s;
     if (rv_status ts = world_top(c)) return ts;   // the exits, from the bits
     if (p.full) {
         if (rv_status s = rv_csdf_build(c)) return s;
@@ -196,6 +213,7 @@ rv_status rv_world_scroll(rv_ctx* c, int32_t dx, int32_t dz) {
         c->scroll_tmp = nullptr;
         c->scroll_tmp_cap = 0;
     }
+    persist_trim(c);
     if (s != RV_OK) return s;
     HIP_TRY(c, se);
     c->scroll_count++;

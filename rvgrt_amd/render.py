@@ -125,6 +125,18 @@ def scroll_view(dx, dz, cam: rv_camera = None, vp=None, prev_vp=None):
     return c2, m[0], m[1]
 
 
+def persist_column_map(log2_dims, bx, bz):
+    """rv_persist_column_map (host only): for each of the 2 Y words of brick column
+    (bx, bz)'s column bits in a world of these log2 dims, the dword index into the
+    brick array that the persistence kernels read or write."""
+    L = _lib.load()
+    out = np.zeros(2 << int(log2_dims[1]), np.uint32)
+    st = L.rv_persist_column_map(int(log2_dims[0]), int(log2_dims[1]), int(log2_dims[2]), int(bx), int(bz), _ptr(out))
+    if st != 0:
+        raise RvError(f"rv_persist_column_map: {_lib.STATUS_NAMES.get(st, st)}")
+    return out
+
+
 def texture_tile_at(ox, oz, pos):
     """rv_texture_tile_at (host only): sampleTexture's atlas tile, a uint8 0xYX per
     position (n, 3) float32, evaluated on the CPU from the noise at texture origin
@@ -409,6 +421,60 @@ class StateRender:
         self._check(self._L.rv_world_scroll_info(self._h, C.byref(n), C.byref(c), C.byref(f), C.byref(ox),
                                                  C.byref(oz)), "rv_world_scroll_info")
         return int(n.value), int(c.value), bool(f.value), (int(ox.value), int(oz.value))
+
+    def world_persist(self, on):
+        """rv_world_persist: edited columns survive scrolling away and back -- the dirty
+        columns that leave the window are kept in a host store and put back when the
+        library generates them again (world_scroll, world_build).  Default off."""
+        self._check(self._L.rv_world_persist(self._h, int(bool(on))), "rv_world_persist")
+
+    def world_persist_info(self) -> dict:
+        """rv_world_persist_info: {on, dirty_columns, stored_columns, stored_bytes,
+        captured_total, restored_total}."""
+        on = C.c_int32()
+        v = [C.c_uint64() for _ in range(5)]
+        self._check(self._L.rv_world_persist_info(self._h, C.byref(on), *[C.byref(x) for x in v]),
+                    "rv_world_persist_info")
+        names = ("dirty_columns", "stored_columns", "stored_bytes", "captured_total", "restored_total")
+        return {"on": bool(on.value), **{k: int(x.value) for k, x in zip(names, v)}}
+
+    def world_persist_flush(self):
+        """rv_world_persist_flush ("save game"): every dirty column of the window is copied
+        into the store; the columns stay dirty.  Synchronous."""
+        self._check(self._L.rv_world_persist_flush(self._h), "rv_world_persist_flush")
+
+    def world_store_list(self) -> np.ndarray:
+        """rv_world_store_list: the store's keys, (n, 2) int32 rows (wx, wz) sorted by (wz, wx)."""
+        n = C.c_int64()
+        self._check(self._L.rv_world_store_list(self._h, None, 0, C.byref(n)), "rv_world_store_list")
+        keys = np.zeros((int(n.value), 2), np.int32)
+        self._check(self._L.rv_world_store_list(self._h, _ptr(keys), len(keys), C.byref(n)), "rv_world_store_list")
+        return keys
+
+    def world_store_get(self, wx, wz) -> np.ndarray:
+        """rv_world_store_get: the stored column bits (2 Y uint32) of key (wx, wz)."""
+        bits = np.zeros(2 * self.dims[1], np.uint32)
+        self._check(self._L.rv_world_store_get(self._h, int(wx), int(wz), _ptr(bits), bits.nbytes), "rv_world_store_get")
+        return bits
+
+    def world_store_put(self, wx, wz, bits):
+        """rv_world_store_put: column bits (2 Y uint32) into the store under key (wx, wz);
+        used the next time the library generates that column."""
+        a = np.ascontiguousarray(bits, np.uint32)
+        self._check(self._L.rv_world_store_put(self._h, int(wx), int(wz), _ptr(a), a.nbytes), "rv_world_store_put")
+
+    def world_store_clear(self):
+        """rv_world_store_clear: empties the store and the dirty set."""
+        self._check(self._L.rv_world_store_clear(self._h), "rv_world_store_clear")
+
+    def world_columns_read(self, bxz) -> np.ndarray:
+        """rv_world_columns_read: the column bits of the grid brick columns (bx, bz) of
+        the list, (n, 2 Y) uint32 in list order (repeats allowed).  Synchronous."""
+        cols = np.ascontiguousarray(bxz, np.int32).reshape(-1, 2)
+        bits = np.zeros((len(cols), 2 * self.dims[1]), np.uint32)
+        self._check(self._L.rv_world_columns_read(self._h, _ptr(cols), len(cols), _ptr(bits), bits.nbytes),
+                    "rv_world_columns_read")
+        return bits
 
     def texture_origin_set(self, ox, oz):
         """rv_texture_origin_set: sampleTexture's lattice points are shifted by (ox, 0, oz)
