@@ -14,6 +14,8 @@ All horizon arrays are [z / 2, x / 2], as rv_world_export returns them.
 """
 import numpy as np
 
+from gpu_world import synthetic_voxels
+
 HORIZON_OFF = 0xFFFFFFFF     # the fills of a table that is switched off (rv_config.exits_off)
 DTOP_OFF = 0x7F7F7F7F
 
@@ -28,8 +30,7 @@ def terrain_cut(oracle, lx, ly, lz, cut=None):
 
 
 def synthetic(kind, X, Y, Z):
-    from test_gpu_synthetic_worlds import _voxels
-    return _voxels(kind, X, Y, Z, np.random.default_rng(sum(map(ord, kind))))
+    return synthetic_voxels(kind, X, Y, Z, np.random.default_rng(sum(map(ord, kind))))
 
 
 def single(X, Y, Z, where):

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_world import sun
 import np_exits as E
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,11 +49,6 @@ def _host_tables(L, lg, vox, sun):
     dt = np.zeros((Z // 8, X // 8), np.int32)
     assert L.rvh_exit_tables(*lg, _p(bits), _p(sun), C.byref(yt), _p(ct), _p(hz), _p(dt)) == 0
     return int(yt.value), ct, hz, dt
-
-
-@pytest.fixture(scope="module")
-def sun(oracle):
-    return np.ascontiguousarray(oracle.sun_dir(), np.float32)
 
 
 @pytest.mark.parametrize("name", list(E.WORLDS))

@@ -4,15 +4,10 @@ margin per axis and clipped to the grid -- against a numpy restatement."""
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 WORLDS = [(7, 7, 7), (8, 6, 7), (4, 4, 4)]
 MARGINS = [0, 1, 5, 1000]   # 1000 cells: larger than every grid here
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def restated(lg, boxes, margin):

@@ -17,17 +17,11 @@ import numpy as np
 import pytest
 
 from conftest import Hip
+from gpu_world import rv
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def _read_ppm(path):

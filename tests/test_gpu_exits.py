@@ -13,29 +13,13 @@ whoever shares its wave."""
 import numpy as np
 import pytest
 
+from gpu_world import rv, sun, tables
 import np_exits as E
 
 pytestmark = pytest.mark.gpu
 
 HIT_FIELDS = ("pos", "normal", "u", "v")
 COUNTS = (("sphere_steps", "n_sphere"), ("dda_steps", "n_dda"), ("csdf_checks", "n_check"))
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-@pytest.fixture(scope="module")
-def sun(oracle):
-    return np.ascontiguousarray(oracle.sun_dir(), np.float32)
-
-
-def _tables(rv, r):
-    return (r.world_top_info(), r.world_export(rv.RV_WORLD_COLTOP), r.world_export(rv.RV_WORLD_HORIZON),
-            r.world_export(rv.RV_WORLD_DTOP))
 
 
 def _context(rv, lg, vox, csdf=False, **kw):
@@ -53,7 +37,7 @@ def test_tables_equal_the_reference(rv, oracle, sun, name):
     vox = make(oracle)
     r = _context(rv, lg, vox)
     try:
-        yt, ct, hz, dt = _tables(rv, r)
+        yt, ct, hz, dt = tables(rv, r)
     finally:
         r.close()
     slack = E.check_tables(E.reference(vox, sun, name), yt, ct, hz, dt, name)
@@ -72,7 +56,7 @@ def test_exits_off_gives_the_documented_fills(rv, oracle, sun):
     for off in (rv.RV_EXIT_SKY, rv.RV_EXIT_COLUMN, rv.RV_EXIT_SUN, rv.RV_EXIT_COLUMN | rv.RV_EXIT_SUN):
         r = _context(rv, lg, vox, exits_off=off)
         try:
-            yt, ct, hz, dt = _tables(rv, r)
+            yt, ct, hz, dt = tables(rv, r)
         finally:
             r.close()
         if off & rv.RV_EXIT_SKY:
@@ -103,7 +87,7 @@ def test_tables_follow_a_second_import(rv, oracle, sun):
     try:
         for what, vox in worlds:
             r.world_import(rv.RV_WORLD_BITS, E.bits_of(vox))
-            E.check_tables(E.reference(vox, sun), *_tables(rv, r), what)
+            E.check_tables(E.reference(vox, sun), *tables(rv, r), what)
     finally:
         r.close()
 
@@ -115,14 +99,14 @@ def test_tables_follow_each_edit(rv, oracle, sun):
     vox = make(oracle)
     r = _context(rv, lg, vox, csdf=True)
     try:
-        E.check_tables(E.reference(vox, sun, "edit0"), *_tables(rv, r), "before the edits")
+        E.check_tables(E.reference(vox, sun, "edit0"), *tables(rv, r), "before the edits")
         for n, (what, boxes) in enumerate(E.edit_steps(vox), 1):
             r.world_edit(boxes)
             edits, cells, full = r.world_edit_info()
             assert edits == n and cells > 0 and not full, (what, edits, cells, full)
             vox = E.apply_boxes(vox, boxes)
             assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), E.bits_of(vox)), what
-            slack = E.check_tables(E.reference(vox, sun, f"edit{n}"), *_tables(rv, r), what)
+            slack = E.check_tables(E.reference(vox, sun, f"edit{n}"), *tables(rv, r), what)
             print(f"{what} {boxes}: local, slack {slack}")
     finally:
         r.close()
@@ -296,7 +280,7 @@ def test_exit_variants_follow_a_pillar_edit(rv, oracle, sun, ray_world):
         r.world_edit(boxes)
         assert r.world_edit_info()[0] == 1 and not r.world_edit_info()[2]
         assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), ow.csdf)
-        E.check_tables(E.reference(E.apply_boxes(vox, boxes), sun, "pillar"), *_tables(rv, r), "pillar")
+        E.check_tables(E.reference(E.apply_boxes(vox, boxes), sun, "pillar"), *tables(rv, r), "pillar")
         for kind, flags in (("col", rv.RV_TRACE_COL), ("sun", rv.RV_TRACE_SUN)):
             ray, before = rays[kind]
             o = ow.trace_batch(*ray)

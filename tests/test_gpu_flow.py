@@ -11,14 +11,9 @@ two launches (rv_set_flow(0)) bit for bit, and the oracle.
 import numpy as np
 import pytest
 
+from gpu_world import draw, rv
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def _make(rv, atlas, lg, W, H, rays, flow, flags=None):
@@ -28,13 +23,6 @@ def _make(rv, atlas, lg, W, H, rays, flow, flags=None):
     r.gi_update(0)
     r.set_flow(flow)
     return r
-
-
-def _draw(r, d):
-    """drawCUDA with ref_compat: the jitterY argument is the frame time (Appendix R1)."""
-    c = d.cam
-    r.draw_cuda(c.pos[:], c.forward[:], c.up[:], c.right[:], np.ctypeslib.as_array(d.vp),
-                np.ctypeslib.as_array(d.prev_vp), 0.0, d.time)
 
 
 def _images(r, rv):
@@ -64,7 +52,7 @@ def test_flow_frames_equal_two_launches_and_oracle(rv, atlas, oracle, monkeypatc
     for k in range(nfr):
         for r in (a, b):
             r.update_gi_data()
-            _draw(r, seq[k])
+            draw(r, seq[k])
         if k % readback_every == 0 or k == nfr - 1:
             for x, y in zip(_images(a, rv), _images(b, rv)):
                 assert np.array_equal(x, y), k
@@ -108,7 +96,7 @@ def test_flow_gi_computed_ahead_is_dropped_when_stale(rv, atlas):
             if op == "u":
                 r.update_gi_data()
             elif op == "d":
-                _draw(r, seq[k % len(seq)])
+                draw(r, seq[k % len(seq)])
             elif op == "g":   # an explicit window in between (rv_gi_update): the kept cells are stale
                 r.gi_update(40, first=777, count=3000)
             elif op == "i":   # a GI import in between
@@ -138,7 +126,7 @@ def test_flow_fallback_evaluates_the_same_texels(rv, atlas, monkeypatch):
     for k in range(3):
         for r in (a, b):
             r.update_gi_data()
-            _draw(r, seq[k])
+            draw(r, seq[k])
         for x, y in zip(_images(a, rv), _images(b, rv)):
             assert np.array_equal(x, y), k
     assert np.array_equal(a.world_export(rv.RV_WORLD_GI), b.world_export(rv.RV_WORLD_GI))
@@ -183,7 +171,7 @@ def test_flow_fallback_throughput_variant_4k(rv, atlas, monkeypatch):
     for k in range(2):
         for r in (a, b):
             r.update_gi_data()
-            _draw(r, seq[k])
+            draw(r, seq[k])
         for x, y in zip(_images(a, rv), _images(b, rv)):
             assert np.array_equal(x, y), k
     assert np.array_equal(a.world_export(rv.RV_WORLD_GI), b.world_export(rv.RV_WORLD_GI))

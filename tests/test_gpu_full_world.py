@@ -25,16 +25,10 @@ own first, and run before them (file order):
 import numpy as np
 import pytest
 
+from gpu_world import rv
 import world_golden as WG
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def _gpu_world(rv, atlas, log2, stages):

@@ -29,17 +29,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_world import rv
 import world_golden as WG
 from conftest import random_rays
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def coarse_solid(bits, dims, z0, z1):

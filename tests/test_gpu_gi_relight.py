@@ -8,6 +8,9 @@ and no cell's update depends on another cell."""
 import numpy as np
 import pytest
 
+from gpu_world import ctx128, draw, edited, gi, gi_dims, oracle_of, rv, sparse_bits
+from np_world import _in_box, _open_centres, expect_relight
+
 pytestmark = pytest.mark.gpu
 
 LG128 = (7, 7, 7)
@@ -15,120 +18,20 @@ EDIT_BOXES = [(37, 30, 21, 46, 52, 28, 1), (30, 20, 18, 41, 36, 30, 0)]
 W, H = 160, 96
 
 
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
 # ---------------------------------------------------------------- helpers
-def _dims(lg):
-    return tuple(1 << (l - 2) for l in lg)
-
-
-def _voxels(bits, lg):
-    X, Y, Z = (1 << l for l in lg)
-    return np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(Z, Y, X).astype(bool)
-
-
-def _edited(bits, lg, boxes):
-    vox = _voxels(bits, lg)
-    for (x0, y0, z0, x1, y1, z1, s) in boxes:
-        vox[z0:z1, y0:y1, x0:x1] = bool(s)
-    return np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
-
-
-def _sparse_bits(lg, density, seed):
-    n = 1 << sum(lg)
-    bits = np.zeros(n // 32, np.uint32)
-    idx = np.random.default_rng(seed).choice(n, int(n * density))
-    np.bitwise_or.at(bits, idx >> 5, (np.uint32(1) << (idx & 31).astype(np.uint32)))
-    return bits
-
-
 def _random_grid(lg, seed=9):
-    n = int(np.prod(_dims(lg)))
+    n = int(np.prod(gi_dims(lg)))
     g = np.random.default_rng(seed).integers(0, 256, n * 4, dtype=np.uint8)
     g[3::4] = 255
     return g
-
-
-def _rows(lg, box):
-    GX, GY, _ = _dims(lg)
-    x0, y0, z0, x1, y1, z1 = box
-    return [x0 + GX * (y + GY * z) for z in range(z0, z1) for y in range(y0, y1)], x1 - x0
-
-
-def _in_box(lg, box):
-    GX, GY, GZ = _dims(lg)
-    m = np.zeros((GZ, GY, GX), bool)
-    x0, y0, z0, x1, y1, z1 = box
-    m[z0:z1, y0:y1, x0:x1] = True
-    return m.ravel()
-
-
-def _open_centres(bits, lg, box):
-    """Box cells whose centre voxel 4c + 2 is not solid: the cells an update traces."""
-    x0, y0, z0, x1, y1, z1 = box
-    c = _voxels(bits, lg)[2::4, 2::4, 2::4]
-    return int((~c[z0:z1, y0:y1, x0:x1]).sum())
-
-
-def expect_relight(ow, box, frame0, steps, init=False, saturate=False, in_place=False):
-    """The relight on the oracle world's grid (changed in place; returned as a uint32 copy).  A step
-    updates the box one x-row at a time, every row from the step's snapshot of the grid;
-    in_place=True lets a row see the rows updated before it in the same step (the wrong answer)."""
-    lg = (ow.lx, ow.ly, ow.lz)
-    rows, nx = _rows(lg, box)
-    g = ow.gi.view(np.uint32)
-    if init:
-        for first in rows:
-            ow.gi_init(first=first, count=nx, saturate=saturate)
-    for i in range(steps):
-        snap = g.copy()
-        new = []
-        for first in rows:
-            if not in_place:
-                g[:] = snap
-            ow.gi_update((frame0 + i) & 0xFFFFFFFF, first, nx)
-            new.append(g[first:first + nx].copy())
-        if not in_place:
-            g[:] = snap
-            for first, v in zip(rows, new):
-                g[first:first + nx] = v
-    return g.copy()
-
-
-def _oracle(oracle, atlas, lg, bits, csdf=None):
-    ow = oracle.OracleWorld(*lg, atlas=atlas)
-    ow.bits[:] = bits
-    if csdf is None:
-        ow.build_csdf()
-    else:
-        ow.csdf[:] = csdf
-    return ow
-
-
-def _gi(rv, r):
-    return r.world_export(rv.RV_WORLD_GI).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
 def edited128(rv, oracle, atlas, oracle_world):
     """The generated 128^3 world after the two-box edit: (bits, csdf), built once, never changed."""
     base = oracle_world(7, 7, 7, gi_sweeps=0)
-    ow = _oracle(oracle, atlas, LG128, _edited(base.bits.copy(), LG128, EDIT_BOXES))
+    ow = oracle_of(oracle, LG128, edited(base.bits.copy(), LG128, EDIT_BOXES), atlas=atlas)
     return ow.bits.copy(), ow.csdf.copy()
-
-
-def _ctx128(rv, atlas, edit=True, **kw):
-    r = rv.StateRender(LG128, W, H, flags=rv.RV_FLAGS_REFERENCE, atlas=atlas, **kw)
-    r.world_build()
-    r.gi_update(0)
-    if edit:
-        r.world_edit(EDIT_BOXES)
-    return r
 
 
 @pytest.fixture(scope="module")
@@ -136,7 +39,7 @@ def sparse16(rv, oracle, atlas):
     """A 16^3 world of 10 %-dense random bits (the generated 16^3 world is all solid): (bits, csdf, grid
     after gi_init)."""
     lg = (4, 4, 4)
-    ow = _oracle(oracle, atlas, lg, _sparse_bits(lg, 0.10, 5))
+    ow = oracle_of(oracle, lg, sparse_bits(lg, 0.10, 5, exact=False), atlas=atlas)
     ow.gi_init()
     return ow.bits.copy(), ow.csdf.copy(), ow.gi.copy()
 
@@ -155,15 +58,15 @@ def test_relight_after_an_edit(rv, oracle, atlas, edited128, init):
     from rvgrt_amd.configs import TEST_POSES_128
     box, frame0, K = (3, 5, 2, 17, 14, 11), 1000, 3
     flags = rv.RV_FLAGS_REFERENCE
-    r = _ctx128(rv, atlas, gi_rays_per_frame=4096)
+    r = ctx128(rv, atlas, W, H, edit=EDIT_BOXES, gi_rays_per_frame=4096)
     assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), edited128[0])
     assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), edited128[1])
-    g0 = _gi(rv, r)
-    ow = _oracle(oracle, atlas, LG128, *edited128)
+    g0 = gi(rv, r)
+    ow = oracle_of(oracle, LG128, *edited128, atlas=atlas)
     ow.gi[:] = g0.view(np.uint8)
     want = expect_relight(ow, box, frame0, K, init=init)
     r.gi_relight(box, frame0, K, init=init)
-    got = _gi(rv, r)
+    got = gi(rv, r)
     changed = int((want != g0).sum())
     print(f"init={init}: {changed} of {int(_in_box(LG128, box).sum())} box cells change")
     assert changed > 0
@@ -176,13 +79,13 @@ def test_relight_after_an_edit(rv, oracle, atlas, edited128, init):
     assert np.array_equal(r.readback(rv.RV_IMAGE_COLOR), ref["rgba"])
     # the frame counter and the rolling offset are untouched: a twin that imported the expected grid
     # goes through the same two rolling updates
-    t = _ctx128(rv, atlas, gi_rays_per_frame=4096)
+    t = ctx128(rv, atlas, W, H, edit=EDIT_BOXES, gi_rays_per_frame=4096)
     t.world_import(rv.RV_WORLD_GI, want)
     for c in (r, t):
         c.update_gi_data()
         c.update_gi_data()
-    after = _gi(rv, r)
-    assert np.array_equal(after, _gi(rv, t))
+    after = gi(rv, r)
+    assert np.array_equal(after, gi(rv, t))
     assert not np.array_equal(after, want)
     r.close()
     t.close()
@@ -193,9 +96,9 @@ def test_relight_after_an_edit(rv, oracle, atlas, edited128, init):
                                             ((7, 5, 6), 0.03, (2, 0, 3, 29, 8, 14))])
 def test_in_box_dependency(rv, oracle, atlas, lg, density, box):
     frame0, K = 500, 3
-    bits = _sparse_bits(lg, density, 3)
+    bits = sparse_bits(lg, density, 3, exact=False)
     grid = _random_grid(lg)
-    ow = _oracle(oracle, atlas, lg, bits)
+    ow = oracle_of(oracle, lg, bits, atlas=atlas)
     ow.gi[:] = grid
     want = expect_relight(ow, box, frame0, K)
     ow.gi[:] = grid
@@ -207,34 +110,34 @@ def test_in_box_dependency(rv, oracle, atlas, lg, density, box):
     r.csdf_build()
     r.world_import(rv.RV_WORLD_GI, grid)
     r.gi_relight(box, frame0, K)
-    assert np.array_equal(_gi(rv, r), want)
+    assert np.array_equal(gi(rv, r), want)
     r.close()
 
 
 # ---------------------------------------------------------------- 3. equivalences with the existing calls
 def test_equivalences_on_a_twin(rv, atlas):
-    GX, GY, GZ = _dims(LG128)
-    r, t = (_ctx128(rv, atlas) for _ in range(2))
-    g0 = _gi(rv, r)
+    GX, GY, GZ = gi_dims(LG128)
+    r, t = (ctx128(rv, atlas, W, H, edit=EDIT_BOXES) for _ in range(2))
+    g0 = gi(rv, r)
     # a slab of whole planes, one step == rv_gi_update over the planes' linear range
     z0, z1 = 5, 12
     r.gi_relight((0, 0, z0, GX, GY, z1), 77, 1)
     t.gi_update(77, z0 * GX * GY, (z1 - z0) * GX * GY)
-    g1 = _gi(rv, r)
-    assert np.array_equal(g1, _gi(rv, t)) and not np.array_equal(g1, g0)
+    g1 = gi(rv, r)
+    assert np.array_equal(g1, gi(rv, t)) and not np.array_equal(g1, g0)
     # the whole grid, two steps == two full sweeps
     r.gi_relight((0, 0, 0, GX, GY, GZ), 0xFFFFFFFF, 2)   # the frame number wraps as uint32
     t.gi_update(0xFFFFFFFF)
     t.gi_update(0)
-    g2 = _gi(rv, r)
-    assert np.array_equal(g2, _gi(rv, t)) and not np.array_equal(g2, g1)
+    g2 = gi(rv, r)
+    assert np.array_equal(g2, gi(rv, t)) and not np.array_equal(g2, g1)
     # composition: 1 + 2 steps == 3 steps
     box = (3, 5, 2, 17, 14, 11)
     r.gi_relight(box, 40, 1)
     r.gi_relight(box, 41, 2)
     t.gi_relight(box, 40, 3)
-    g3 = _gi(rv, r)
-    assert np.array_equal(g3, _gi(rv, t)) and not np.array_equal(g3, g2)
+    g3 = gi(rv, r)
+    assert np.array_equal(g3, gi(rv, t)) and not np.array_equal(g3, g2)
     assert r.gi_relight_info() == (4, GX * GY * (z1 - z0) + GX * GY * GZ + 2 * 1134,
                                    GX * GY * (z1 - z0) + 2 * GX * GY * GZ + 3 * 1134)
     r.close()
@@ -244,13 +147,13 @@ def test_equivalences_on_a_twin(rv, atlas):
 @pytest.mark.parametrize("saturate", [False, True])
 def test_init_alone_equals_the_oracle_rows(rv, oracle, atlas, edited128, saturate):
     box = (19, 11, 6, 30, 24, 13)   # 11 x 13 x 7 cells across the terrain's surface: lit and shadowed cells
-    r = _ctx128(rv, atlas, gi_init_saturate=saturate)
-    g0 = _gi(rv, r)
-    ow = _oracle(oracle, atlas, LG128, *edited128)
+    r = ctx128(rv, atlas, W, H, edit=EDIT_BOXES, gi_init_saturate=saturate)
+    g0 = gi(rv, r)
+    ow = oracle_of(oracle, LG128, *edited128, atlas=atlas)
     ow.gi[:] = g0.view(np.uint8)
     want = expect_relight(ow, box, 0, 0, init=True, saturate=saturate)
     r.gi_relight(box, 0, 0, init=True)
-    got = _gi(rv, r)
+    got = gi(rv, r)
     assert np.array_equal(got, want)
     inb = _in_box(LG128, box)
     lit = 0xFFFFFFFF if saturate else 0xFFFEF7F6
@@ -268,11 +171,11 @@ def test_smallest_world(rv, oracle, atlas, sparse16):
     any_corner = False
     for box, K in cases:
         r.world_import(rv.RV_WORLD_GI, sparse16[2])
-        ow = _oracle(oracle, atlas, lg, sparse16[0], sparse16[1])
+        ow = oracle_of(oracle, lg, sparse16[0], sparse16[1], atlas=atlas)
         ow.gi[:] = sparse16[2]
         want = expect_relight(ow, box, 300, K)
         r.gi_relight(box, 300, K)
-        assert np.array_equal(_gi(rv, r), want), box
+        assert np.array_equal(gi(rv, r), want), box
         changed = int((want != sparse16[2].view(np.uint32)).sum())
         print(f"{box} K={K}: {changed} cells change")
         if K > 2:
@@ -285,13 +188,13 @@ def test_smallest_world(rv, oracle, atlas, sparse16):
 
 def test_odd_box_dims(rv, oracle, atlas, edited128):
     box = (6, 9, 3, 11, 12, 10)   # 5 x 3 x 7 cells around the floor: no dimension a multiple of the 4-cell block
-    r = _ctx128(rv, atlas)
-    g0 = _gi(rv, r)
-    ow = _oracle(oracle, atlas, LG128, *edited128)
+    r = ctx128(rv, atlas, W, H, edit=EDIT_BOXES)
+    g0 = gi(rv, r)
+    ow = oracle_of(oracle, LG128, *edited128, atlas=atlas)
     ow.gi[:] = g0.view(np.uint8)
     want = expect_relight(ow, box, 12, 2)
     r.gi_relight(box, 12, 2)
-    assert np.array_equal(_gi(rv, r), want)
+    assert np.array_equal(gi(rv, r), want)
     assert (want != g0).any()
     r.close()
 
@@ -300,7 +203,7 @@ def test_odd_box_dims(rv, oracle, atlas, edited128):
 def test_status_behaviour(rv, atlas):
     from rvgrt_amd.configs import TEST_POSES_128, camera_path
     lg = (7, 6, 7)
-    GX, GY, GZ = _dims(lg)
+    GX, GY, GZ = gi_dims(lg)
     flags = rv.RV_FLAGS_REFERENCE
     r = rv.StateRender(lg, W, H, flags=flags, atlas=atlas, gi_rays_per_frame=2048)
     with pytest.raises(rv.RvError, match="RV_ERR_STATE"):
@@ -310,7 +213,7 @@ def test_status_behaviour(rv, atlas):
     r.gi_relight((1, 2, 3, 9, 7, 8), 5, 2)
     info = r.gi_relight_info()
     assert info == (1, 8 * 5 * 5, 2 * 8 * 5 * 5)
-    grid = _gi(rv, r)
+    grid = gi(rv, r)
     good = (1, 1, 1, 4, 4, 4)
     bad = [(4, 4, 4, 4, 5, 5), (4, 4, 4, 5, 3, 5), (4, 4, 4, 5, 5, 4),                      # empty / reversed
            (-1, 0, 0, 1, 1, 1), (0, -1, 0, 1, 1, 1), (0, 0, -1, 1, 1, 1),                   # below the grid
@@ -335,7 +238,7 @@ def test_status_behaviour(rv, atlas):
         assert L.rv_gi_relight(r._h, b, 0, 1, fl) == rv._lib.RV_ERR_INVALID
     assert L.rv_gi_relight(r._h, None, 0, 1, 0) == rv._lib.RV_ERR_INVALID
     assert r.gi_relight_info() == info
-    assert np.array_equal(_gi(rv, r), grid)
+    assert np.array_equal(gi(rv, r), grid)
     # the call with nothing to do invalidates nothing: the pre-pass and GI update the pipelined loop keeps
     # for the next call survive it (a kept update is applied by the next call, not recomputed)
     seq = camera_path(TEST_POSES_128["P0"], W, H, 6, pan=0.01, ref_compat=True)
@@ -352,7 +255,7 @@ def test_status_behaviour(rv, atlas):
         c.render_frame_seq(seq[3:6], next_desc=None, flags=flags, gi_per_frame=True)
     assert r.stats()["gi_traces"] == t.stats()["gi_traces"]   # nothing recomputed on r's side
     assert np.array_equal(r.readback(rv.RV_IMAGE_COLOR), t.readback(rv.RV_IMAGE_COLOR))
-    assert np.array_equal(_gi(rv, r), _gi(rv, t))
+    assert np.array_equal(gi(rv, r), gi(rv, t))
     # the largest call the bound admits works
     r.gi_relight(whole, 3, kmax)
     assert r.gi_relight_info() == (2, info[1] + GX * GY * GZ, info[2] + kmax * GX * GY * GZ)
@@ -361,12 +264,6 @@ def test_status_behaviour(rv, atlas):
 
 
 # ---------------------------------------------------------------- 6. work computed ahead is discarded
-def _draw(r, d):
-    c = d.cam
-    r.draw_cuda(c.pos[:], c.forward[:], c.up[:], c.right[:], np.ctypeslib.as_array(d.vp),
-                np.ctypeslib.as_array(d.prev_vp), 0.0, d.time)
-
-
 @pytest.mark.parametrize("mode,in_flight", [("draw", 1), ("seq", 1), ("group", 1), ("draw", 2), ("seq", 2)])
 def test_frames_across_a_relight(rv, atlas, mode, in_flight):
     """renderLoop's frames before and after a relight.  A: the defaults -- flow frames whose launch computes
@@ -378,7 +275,7 @@ def test_frames_across_a_relight(rv, atlas, mode, in_flight):
     n = 4 if mode == "group" else 3
     box = (19, 11, 6, 30, 24, 13)   # across the terrain's surface
     seq = camera_path(TEST_POSES_128["P0"], W, H, 2 * n, pan=0.01, ref_compat=True)
-    a, b = (_ctx128(rv, atlas, edit=False, gi_rays_per_frame=4096) for _ in range(2))
+    a, b = (ctx128(rv, atlas, W, H, gi_rays_per_frame=4096) for _ in range(2))
     if mode == "draw":
         b.set_flow(0)
         b.set_gi_async(0)
@@ -396,19 +293,19 @@ def test_frames_across_a_relight(rv, atlas, mode, in_flight):
             if mode == "draw":
                 for k in range(k0, k0 + n):
                     c.update_gi_data()
-                    _draw(c, seq[k])
+                    draw(c, seq[k])
             else:
                 c.render_frame_seq(seq[k0:k0 + n], next_desc=seq[k0 + n] if k0 == 0 else None, flags=flags,
                                    gi_per_frame=True)
         for k in (rv.RV_IMAGE_COLOR, rv.RV_IMAGE_MOTION, rv.RV_IMAGE_DEPTH):
             assert np.array_equal(a.readback(k), b.readback(k)), (k0, k)
-        assert np.array_equal(_gi(rv, a), _gi(rv, b)), k0
+        assert np.array_equal(gi(rv, a), gi(rv, b)), k0
     run(0)
-    before = _gi(rv, a)
+    before = gi(rv, a)
     for c in (a, b):
         c.gi_relight(box, 9000, 4, init=True)
-    relit = _gi(rv, a)
-    assert np.array_equal(relit, _gi(rv, b))
+    relit = gi(rv, a)
+    assert np.array_equal(relit, gi(rv, b))
     assert (relit != before).any() and not (relit != before)[~_in_box(LG128, box)].any()
     run(n)
     assert a.flow_info()[2] == 0
@@ -420,7 +317,7 @@ def test_frames_across_a_relight(rv, atlas, mode, in_flight):
 
 # ---------------------------------------------------------------- 7. counters
 def test_counters(rv, atlas, edited128):
-    r = _ctx128(rv, atlas)
+    r = ctx128(rv, atlas, W, H, edit=EDIT_BOXES)
     total = (0, 0, 0)
     for box, K, init in [((3, 5, 2, 17, 14, 11), 3, False), ((3, 5, 2, 17, 14, 11), 2, True),
                          ((6, 9, 3, 11, 12, 10), 0, True), ((0, 0, 0, 4, 4, 4), 1, False)]:

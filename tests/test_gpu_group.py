@@ -8,14 +8,9 @@ group size, over calls of any length, with rolling GI windows that wrap
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def _make(rv, atlas, lg, W, H, rays, sweeps=1):

@@ -10,15 +10,9 @@ rows rendered on the GPU's exported world -- all bit for bit.
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 pytestmark = pytest.mark.gpu
-
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 @pytest.mark.timeout(900)

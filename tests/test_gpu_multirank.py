@@ -14,14 +14,9 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_world import run_ranks, rv
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 LG, W, H, RAYS = 7, 320, 192, 5000
@@ -32,26 +27,6 @@ def _make(rv, atlas, flags):
     r.world_build()
     r.gi_update(0)
     return r
-
-
-def _run_ranks(fns):
-    """Runs fns[q]() on N threads; re-raises the first failure."""
-    errs = [None] * len(fns)
-
-    def body(q):
-        try:
-            fns[q]()
-        except BaseException as e:   # noqa: BLE001 -- reported below
-            errs[q] = e
-    ts = [threading.Thread(target=body, args=(q,)) for q in range(len(fns))]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout=300)
-        assert not t.is_alive(), "a rank thread hung"
-    for e in errs:
-        if e is not None:
-            raise e
 
 
 @pytest.mark.parametrize("flags,T,N,w0,bpp,grp", [
@@ -79,8 +54,8 @@ def test_loopback_ranks_equal_one_context(rv, atlas, flags, T, N, w0, bpp, grp):
         comms.append(rv.Comm.loopback(r, group, q))
     done = 0
     for a, b, nxt in ((0, 4, 4), (4, 11, None)):   # two calls: the second starts from the kept work
-        _run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[nxt] if nxt else None, flags=flags,
-                                                       gi_per_frame=gi, comm=comms[q]) for q in range(N)])
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[nxt] if nxt else None, flags=flags,
+                                                      gi_per_frame=gi, comm=comms[q]) for q in range(N)])
         for c in comms:
             c.wait(60000)
         for k in range(done, b):
@@ -146,7 +121,7 @@ def test_loopback_disagreement_after_agreed_call_is_rejected(rv, atlas):
         comms.append(rv.Comm.loopback(r, group, q))
     from rvgrt_amd.configs import TEST_POSES_128
     cam, vp = rv.camera_from_pose(*TEST_POSES_128["P0"], W, H)
-    _run_ranks([lambda q=q: rs[q].render_frames(2, cam, vp, comm=comms[q]) for q in range(2)])
+    run_ranks([lambda q=q: rs[q].render_frames(2, cam, vp, comm=comms[q]) for q in range(2)])
     for c in comms:
         c.wait(60000)
     rs[1].set_tile_shard(16, 1, 2, root_weight=0.8)
@@ -234,9 +209,9 @@ def test_loopback_ranks_full_size(rv, atlas, monkeypatch, cfgname, N, w0, grp):
         assert rs[0].frame_group_effective() == grp
     done = 0
     for a, b, nxt in ((0, 17, 17), (17, 20, None)):
-        _run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[nxt] if nxt else None,
-                                                       flags=cfg.flags, gi_per_frame=True, comm=comms[q])
-                    for q in range(N)])
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[nxt] if nxt else None,
+                                                      flags=cfg.flags, gi_per_frame=True, comm=comms[q])
+                   for q in range(N)])
         for c in comms:
             c.wait(120000)
         for k in range(done, b):

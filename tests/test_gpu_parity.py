@@ -12,15 +12,9 @@ import numpy as np
 import pytest
 
 from conftest import Hip as _Hip, random_rays
+from gpu_world import ZERO_SEED_CELL, ZERO_SEED_FRAME, rv
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def _gpu_world(rv, atlas, lx, ly, lz, W=64, H=64, flags=None, seed=(0, 0), gi_sweeps=1):
@@ -63,9 +57,8 @@ def test_gi_sweeps_bit_exact(rv, atlas, oracle_world, oracle):
 
 def test_gi_update_zero_rng_state(rv, atlas, oracle_world, oracle):
     """The cell whose xorshift state idx + frame * 198491317 wraps to 0
-    (tests/test_oracle.py ZERO_SEED_*): the update terminates and agrees
+    (tests/gpu_world.py ZERO_SEED_*): the update terminates and agrees
     with the oracle (a zero state once hung the GPU, 476 frames into a C4 run)."""
-    from test_oracle import ZERO_SEED_CELL, ZERO_SEED_FRAME
     ow = oracle_world(6, 6, 6, gi_sweeps=1)
     r = _gpu_world(rv, atlas, 6, 6, 6, gi_sweeps=1)
     w2 = oracle.OracleWorld(6, 6, 6, atlas=atlas)

@@ -7,6 +7,8 @@ launches keep the contiguous order whatever the option says."""
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 pytestmark = pytest.mark.gpu
 
 LG = 7
@@ -25,13 +27,6 @@ def mixes(W, H):
     """Pattern 0 and every pattern x head of the A/B; the heads from this frame's pre-pass rows."""
     rows = (((W // 2 + 7) // 8) * ((H // 2 + 7) // 8) + 7) // 8   # 60 waves of 8x8 texels: 8 rows
     return [0] + [pack(h, p) for p in PATTERNS for h in (0, rows // 8, rows // 4)] + [pack(0, p) for p in MORE]
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def make(rv, atlas, W, H, flags=None):

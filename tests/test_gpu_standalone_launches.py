@@ -4,14 +4,9 @@ the tile, against the CPU oracle."""
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 _ODD_FRAME = {}

@@ -16,41 +16,9 @@ import numpy as np
 import pytest
 
 from conftest import random_rays
+from gpu_world import run_ranks, rv, synthetic_voxels
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-def _voxels(kind, X, Y, Z, rng):
-    """Dense [z, y, x] occupancy of one synthetic world."""
-    if kind == "empty":
-        return np.zeros((Z, Y, X), bool)
-    if kind == "full":
-        return np.ones((Z, Y, X), bool)
-    if kind == "sparse":
-        return rng.uniform(size=(Z, Y, X)) < 0.01
-    if kind == "dense":
-        return rng.uniform(size=(Z, Y, X)) < 0.40
-    if kind == "pillars":            # a floor and 1-voxel pillars of mixed heights every 6 voxels
-        v = np.zeros((Z, Y, X), bool)
-        v[:, :8, :] = True
-        h = rng.integers(10, Y - 10, (Z // 6 + 1, X // 6 + 1))
-        for k in range(0, Z, 6):
-            for i in range(0, X, 6):
-                v[k, :h[k // 6, i // 6], i] = True
-        return v
-    if kind == "blocks":             # 4^3 blocks at 10 %, with a floor (ragged dims)
-        b = rng.uniform(size=(Z // 4, Y // 4, X // 4)) < 0.10
-        v = b.repeat(4, 0).repeat(4, 1).repeat(4, 2)
-        v[:, :2, :] = True
-        return v
-    raise ValueError(kind)
 
 
 WORLDS = [("empty", (7, 7, 7)), ("full", (6, 6, 6)), ("sparse", (7, 7, 7)), ("dense", (6, 6, 6)),
@@ -64,7 +32,7 @@ def test_synthetic_world_bit_exact(rv, atlas, oracle, kind, dims):
     ow = oracle.OracleWorld(lx, ly, lz, atlas=atlas)
     X, Y, Z = ow.X, ow.Y, ow.Z
     rng = np.random.default_rng(sum(map(ord, kind)))
-    vox = _voxels(kind, X, Y, Z, rng)
+    vox = synthetic_voxels(kind, X, Y, Z, rng)
     ow.bits[:] = np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
     ow.build_csdf()
     ow.gi_init()
@@ -127,7 +95,7 @@ def test_synthetic_world_drop_in_flow(rv, atlas, oracle, kind, dims):
     lx, ly, lz = dims
     ow = oracle.OracleWorld(lx, ly, lz, atlas=atlas)
     X, Y, Z = ow.X, ow.Y, ow.Z
-    vox = _voxels(kind, X, Y, Z, np.random.default_rng(sum(map(ord, kind))))
+    vox = synthetic_voxels(kind, X, Y, Z, np.random.default_rng(sum(map(ord, kind))))
     ow.bits[:] = np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
     ow.build_csdf()
     ow.gi_init()
@@ -343,7 +311,6 @@ def test_odd_resolution_loopback_ranks(rv, atlas, flags, T, N, grp):
     """The N-rank loop (loopback communicator, one host thread per rank; see test_gpu_multirank.py) at
     161 x 97: partial tiles on the right and bottom edges, the gather and rank 0's assembly -- rank 0's
     frames and every rank's GI grid equal one context rendering whole frames one at a time."""
-    import threading
     from rvgrt_amd.configs import TEST_POSES_128, camera_path
     W, H, rays = 161, 97, 3000
     gi = bool(flags & rv.RV_F_GI)
@@ -367,22 +334,8 @@ def test_odd_resolution_loopback_ranks(rv, atlas, flags, T, N, grp):
             r.set_tile_shard(T, q, N)
             r.set_frame_group(grp)
             comms.append(rv.Comm.loopback(r, group, q))
-        errs = [None] * N
-
-        def body(q):
-            try:
-                rs[q].render_frame_seq(seq[0:6], next_desc=seq[6], flags=flags, gi_per_frame=gi, comm=comms[q])
-            except BaseException as e:   # noqa: BLE001 -- re-raised below
-                errs[q] = e
-        ts = [threading.Thread(target=body, args=(q,)) for q in range(N)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join(timeout=300)
-            assert not t.is_alive(), "a rank thread hung"
-        for e in errs:
-            if e is not None:
-                raise e
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[0:6], next_desc=seq[6], flags=flags, gi_per_frame=gi,
+                                                      comm=comms[q]) for q in range(N)])
         for c in comms:
             c.wait(60000)
         for d in seq[0:6]:

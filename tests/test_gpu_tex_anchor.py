@@ -6,11 +6,10 @@ CPU, itself pinned by tests/test_tex_anchor.py against numpy), whole frames and
 GI updates of tests/np_shade.py with the anchored tile of tests/np_tex_anchor.py
 patched in (ray cast: the oracle's), and twin contexts created at the scrolled
 seed that compute nothing ahead.  Every comparison is bit-exact."""
-import threading
-
 import numpy as np
 import pytest
 
+from gpu_world import ctx128, dims, draw, gi, images, run_ranks, rv, same_frames, shifted
 import np_shade as S
 import np_tex_anchor as A
 
@@ -18,31 +17,6 @@ pytestmark = pytest.mark.gpu
 
 W, H = 96, 64
 ORIGIN = (40, -16)
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-def _dims(lg):
-    return tuple(1 << l for l in lg)
-
-
-def _images(rv, r):
-    return [r.readback(k) for k in (rv.RV_IMAGE_COLOR, rv.RV_IMAGE_MOTION, rv.RV_IMAGE_DEPTH)]
-
-
-def _gi(rv, r):
-    return r.world_export(rv.RV_WORLD_GI).view(np.uint32)
-
-
-def _same_frames(rv, r, t, what):
-    for a, b in zip(_images(rv, r), _images(rv, t)):
-        assert np.array_equal(a, b), what
-    assert np.array_equal(_gi(rv, r), _gi(rv, t)), what
 
 
 def _table_positions(r):
@@ -135,10 +109,10 @@ def test_frames_equal_numpy(rv, oracle, atlas, pose, table):
     r.world_build()
     r.gi_update(0)
     r.frame(cam, vp, prev_vp=pvp, time=0.37, flags=flags)
-    color0, mv0, depth0 = _images(rv, r)
+    color0, mv0, depth0 = images(rv, r)
     r.texture_origin_set(*ORIGIN)
     r.frame(cam, vp, prev_vp=pvp, time=0.37, flags=flags)
-    color, mv, depth = _images(rv, r)
+    color, mv, depth = images(rv, r)
     bad = np.any(color != want["rgba"], axis=-1)
     assert not bad.any(), f"{bad.sum()} pixels differ, first at {np.argwhere(bad)[:5].tolist()}"
     assert np.array_equal(mv, want["mv"]) and (mv != 0).any()
@@ -178,20 +152,8 @@ MOVES = {0: [(8, 0), (-24, 0), (64, 0), (8, -8), (256, 0)], 2: [(0, 8), (0, -24)
 
 
 def _pose(lg):
-    X, Y, Z = _dims(lg)
+    X, Y, Z = dims(lg)
     return ((X / 2 + 3.3, 62.0, Z / 2 + 1.7), 2.44, -3.6)
-
-
-def _shifted(rv, d, dx, dz):
-    cam, vp, pvp = rv.scroll_view(dx, dz, d.cam, np.ctypeslib.as_array(d.vp), np.ctypeslib.as_array(d.prev_vp))
-    return rv.frame_desc(cam, vp, pvp, d.time, d.jitter_x, d.jitter_y)
-
-
-def _draw(r, d):
-    c = d.cam
-    r.update_gi_data()
-    r.draw_cuda(c.pos[:], c.forward[:], c.up[:], c.right[:], np.ctypeslib.as_array(d.vp),
-                np.ctypeslib.as_array(d.prev_vp), 0.0, d.time)
 
 
 def _scroll_ctx(rv, atlas, lg, seed, table=1):
@@ -216,18 +178,18 @@ def _frames_three_ways(rv, r, t, descs, what):
     launches = r.flow_info()[1]
     r.set_flow(1)
     for d in descs[:2]:
-        _draw(r, d)
-        _draw(t, d)
-    _same_frames(rv, r, t, (what, "flow"))
+        draw(r, d, update_gi=True)
+        draw(t, d, update_gi=True)
+    same_frames(rv, r, t, (what, "flow"))
     assert r.flow_info()[1] == launches + 2 and r.flow_info()[2] == 0
     r.set_flow(0)
     for d in descs[2:4]:
-        _draw(r, d)
-        _draw(t, d)
-    _same_frames(rv, r, t, (what, "two-launch"))
+        draw(r, d, update_gi=True)
+        draw(t, d, update_gi=True)
+    same_frames(rv, r, t, (what, "two-launch"))
     for c in (r, t):
         c.render_frame_seq(descs[4:7], next_desc=descs[7], flags=flags, gi_per_frame=True)
-    _same_frames(rv, r, t, (what, "seq"))
+    same_frames(rv, r, t, (what, "seq"))
 
 
 @pytest.mark.parametrize("lg,axis", [((8, 6, 6), 0), ((6, 6, 8), 2)])
@@ -265,10 +227,10 @@ def test_table_scrolled_equals_table_rebuilt(rv, atlas, lg, axis):
         t.texture_origin_set(*origin)
         assert np.array_equal(t.texture_tiles(pos), want), what
         r.gi_init()
-        assert np.array_equal(_gi(rv, r), _gi(rv, t)), what
+        assert np.array_equal(gi(rv, r), gi(rv, t)), what
         # the camera path re-expressed in the moved grid (rv_scroll_view) while that keeps it inside the window
         sx, sz = (dx, dz) if max(abs(dx), abs(dz)) <= 64 else (0, 0)
-        _frames_three_ways(rv, r, t, [_shifted(rv, d, sx, sz) for d in seq], what)
+        _frames_three_ways(rv, r, t, [shifted(rv, d, sx, sz) for d in seq], what)
         t.close()
     r.close()
     n.close()
@@ -290,8 +252,8 @@ def test_scrolled_frames_without_a_table_equal_the_table_context(rv, atlas):
         moved = [moved[0] + dx, moved[1] + dz]
         for d in seq:
             for c in (a, b):
-                _draw(c, _shifted(rv, d, moved[0], moved[1]))
-        _same_frames(rv, a, b, (dx, dz))
+                draw(c, shifted(rv, d, moved[0], moved[1]), update_gi=True)
+        same_frames(rv, a, b, (dx, dz))
     col = a.readback(rv.RV_IMAGE_COLOR)
     assert len(np.unique(col.reshape(-1, 4), axis=0)) > 50     # a frame of textured terrain
     a.close()
@@ -324,13 +286,6 @@ def test_there_and_back_and_follow_off(rv, lg, axis):
 
 
 # ---------------------------------------------------------------- 4. work computed ahead is discarded
-def _ctx128(rv, atlas, rays=4096):
-    c = rv.StateRender((7, 7, 7), W, H, flags=rv.RV_FLAGS_REFERENCE, atlas=atlas, gi_rays_per_frame=rays)
-    c.world_build()
-    c.gi_update(0)
-    return c
-
-
 @pytest.mark.parametrize("mode", ["draw", "seq"])
 def test_origin_set_discards_work_computed_ahead(rv, atlas, mode):
     """Every update covers the whole grid (32,768 cells), so that each one reads enough textures to depend on
@@ -338,27 +293,28 @@ def test_origin_set_discards_work_computed_ahead(rv, atlas, mode):
     from rvgrt_amd.configs import TEST_POSES_128, camera_path
     flags = rv.RV_FLAGS_REFERENCE
     seq = camera_path(TEST_POSES_128["P0"], W, H, 5, pan=0.01, ref_compat=True)
-    r, t, u = _ctx128(rv, atlas, 32768), _plain(_ctx128(rv, atlas, 32768)), _plain(_ctx128(rv, atlas, 32768))
+    r, t, u = (ctx128(rv, atlas, W, H, 32768), _plain(ctx128(rv, atlas, W, H, 32768)),
+               _plain(ctx128(rv, atlas, W, H, 32768)))
 
     def run(ctxs, k0, k1):
         for c in ctxs:
             if mode == "draw":
                 for d in seq[k0:k1]:
-                    _draw(c, d)
+                    draw(c, d, update_gi=True)
             else:
                 c.render_frame_seq(seq[k0:k1], next_desc=seq[k1], flags=flags, gi_per_frame=True)
 
     run((r, t, u), 0, 2)
-    _same_frames(rv, r, t, "before the set")
+    same_frames(rv, r, t, "before the set")
     for c in (r, t):
         c.texture_origin_set(*ORIGIN)
     run((r, t), 2, 3)
-    _same_frames(rv, r, t, "frame 3")
+    same_frames(rv, r, t, "frame 3")
     # u never sets the origin: its grid differs, so the frames' updates do read the textures that changed
     run((u,), 2, 3)
-    assert not np.array_equal(_gi(rv, u), _gi(rv, t))
+    assert not np.array_equal(gi(rv, u), gi(rv, t))
     run((r, t), 3, 4)
-    _same_frames(rv, r, t, "frame 4")
+    same_frames(rv, r, t, "frame 4")
     if mode == "draw":
         assert r.flow_info()[0] and r.flow_info()[1] == 4 and r.flow_info()[2] == 0 and not t.flow_info()[0]
     for c in (r, t, u):
@@ -370,7 +326,7 @@ def test_setting_the_current_origin_keeps_the_work_computed_ahead(rv, atlas, mod
     from rvgrt_amd.configs import TEST_POSES_128, camera_path
     flags = rv.RV_FLAGS_REFERENCE
     seq = camera_path(TEST_POSES_128["P0"], W, H, 5, pan=0.01, ref_compat=True)
-    a, b = _ctx128(rv, atlas), _ctx128(rv, atlas)
+    a, b = ctx128(rv, atlas, W, H, 4096), ctx128(rv, atlas, W, H, 4096)
     for c in (a, b):
         c.texture_origin_set(*ORIGIN)
 
@@ -378,14 +334,14 @@ def test_setting_the_current_origin_keeps_the_work_computed_ahead(rv, atlas, mod
         for c in (a, b):
             if mode == "draw":
                 for d in seq[k0:k1]:
-                    _draw(c, d)
+                    draw(c, d, update_gi=True)
             else:
                 c.render_frame_seq(seq[k0:k1], next_desc=seq[k1], flags=flags, gi_per_frame=True)
 
     run(0, 2)
     a.texture_origin_set(*ORIGIN)
     run(2, 4)
-    _same_frames(rv, a, b, "after setting the origin it has")
+    same_frames(rv, a, b, "after setting the origin it has")
     assert a.stats() == b.stats()              # a discarded update or pre-pass would have been traced again
     assert a.flow_info() == b.flow_info()
     a.close()
@@ -393,35 +349,16 @@ def test_setting_the_current_origin_keeps_the_work_computed_ahead(rv, atlas, mod
 
 
 # ---------------------------------------------------------------- 5. two-rank loopback
-def _run_ranks(fns):
-    errs = [None] * len(fns)
-
-    def body(q):
-        try:
-            fns[q]()
-        except BaseException as e:   # noqa: BLE001 -- re-raised below
-            errs[q] = e
-    ts = [threading.Thread(target=body, args=(q,)) for q in range(len(fns))]
-    for th in ts:
-        th.start()
-    for th in ts:
-        th.join(timeout=300)
-        assert not th.is_alive(), "a rank thread hung"
-    for e in errs:
-        if e is not None:
-            raise e
-
-
 def test_two_rank_loop_with_a_following_scroll_equals_one_rank(rv, atlas):
     from rvgrt_amd.configs import TEST_POSES_128, camera_path
     N, (dx, dz) = 2, (-8, 16)
     flags = rv.RV_FLAGS_REFERENCE
     seq = camera_path(TEST_POSES_128["P0"], W, H, 8, pan=0.02, ref_compat=True)
-    seq = seq[:4] + [_shifted(rv, d, dx, dz) for d in seq[4:]]
-    ref = _ctx128(rv, atlas)
+    seq = seq[:4] + [shifted(rv, d, dx, dz) for d in seq[4:]]
+    ref = ctx128(rv, atlas, W, H, 4096)
     ref.set_pipeline(0)
     group = rv.LoopbackGroup(N, timeout_ms=60000)
-    rs = [_ctx128(rv, atlas) for _ in range(N)]
+    rs = [ctx128(rv, atlas, W, H, 4096) for _ in range(N)]
     comms = []
     for q, c in enumerate(rs):
         c.set_tile_shard(32, q, N)
@@ -434,8 +371,8 @@ def test_two_rank_loop_with_a_following_scroll_equals_one_rank(rv, atlas):
             for c in rs + [ref]:
                 c.world_scroll(dx, dz)
                 assert c.texture_origin() == ((ORIGIN[0] + dx, ORIGIN[1] + dz), True)
-        _run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b] if b < 8 else None, flags=flags,
-                                                       gi_per_frame=True, comm=comms[q]) for q in range(N)])
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b] if b < 8 else None, flags=flags,
+                                                      gi_per_frame=True, comm=comms[q]) for q in range(N)])
         for m in comms:
             m.wait(60000)
         for k in range(a, b):

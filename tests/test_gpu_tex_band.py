@@ -9,18 +9,9 @@ the table (rv_config.tex_table = -1), which evaluates the noise for every hit.
 import numpy as np
 import pytest
 
+from gpu_world import pack, rv
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-def _bits(vox):
-    return np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
 
 
 def test_rows_above_the_table_take_the_noise(rv, atlas, oracle_world, monkeypatch):
@@ -35,11 +26,11 @@ def test_rows_above_the_table_take_the_noise(rv, atlas, oracle_world, monkeypatc
 
     def context(table):
         r = rv.StateRender((7, 7, 7), W, H, flags=rv.RV_FLAGS_REFERENCE, atlas=atlas, tex_table=0 if table else -1)
-        r.world_import(rv.RV_WORLD_BITS, _bits(low))   # the table's world
+        r.world_import(rv.RV_WORLD_BITS, pack(low))   # the table's world
         return r
 
     def frames(r, vox):
-        r.world_import(rv.RV_WORLD_BITS, _bits(vox))
+        r.world_import(rv.RV_WORLD_BITS, pack(vox))
         r.csdf_build()
         r.gi_init()
         out = []

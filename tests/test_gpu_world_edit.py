@@ -4,57 +4,16 @@ is a twin -- a second context driven through the same calls that receives
 world_import(BITS, numpy-edited export) + csdf_build() where the first receives
 world_edit -- and the oracle's set_solid + build_csdf.  Every comparison is
 bit-exact."""
-import threading
-
 import numpy as np
 import pytest
 
 from conftest import random_rays
+from gpu_world import (block_in_view, draw, edited, run_ranks, rv, same_frames, same_world, sparse_bits,
+                       twin_edit, voxels)
 
 pytestmark = pytest.mark.gpu
 
 LONG_WORLDS = [(10, 6, 6), (6, 10, 6), (6, 6, 10)]
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-def _voxels(bits, lg):
-    X, Y, Z = (1 << l for l in lg)
-    return np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(Z, Y, X).astype(bool)
-
-
-def _edited(bits, lg, boxes):
-    """The canonical bit words after the boxes, applied in order on the host."""
-    vox = _voxels(bits, lg)
-    for (x0, y0, z0, x1, y1, z1, s) in boxes:
-        vox[z0:z1, y0:y1, x0:x1] = bool(s)
-    return np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
-
-
-def _twin_edit(rv, t, lg, boxes):
-    t.world_import(rv.RV_WORLD_BITS, _edited(t.world_export(rv.RV_WORLD_BITS), lg, boxes))
-    t.csdf_build()
-
-
-def _same_world(rv, r, t, what):
-    bits = r.world_export(rv.RV_WORLD_BITS)
-    csdf = r.world_export(rv.RV_WORLD_CSDF)
-    assert np.array_equal(bits, t.world_export(rv.RV_WORLD_BITS)), what
-    assert np.array_equal(csdf, t.world_export(rv.RV_WORLD_CSDF)), what
-    return bits, csdf
-
-
-def _sparse_bits(lg, density, seed):
-    n = 1 << sum(lg)
-    bits = np.zeros(n // 32, np.uint32)
-    idx = np.random.default_rng(seed).choice(n, int(round(n * density)), replace=False)
-    np.bitwise_or.at(bits, idx >> 5, (np.uint32(1) << (idx & 31).astype(np.uint32)))
-    return bits
 
 
 # ---------------------------------------------------------------- 1. locality and equality
@@ -63,7 +22,7 @@ def test_local_rebuild_equals_full_rebuild(rv, oracle, lg):
     X, Y, Z = (1 << l for l in lg)
     ncells = X * Y * Z // 8
     ow = oracle.OracleWorld(*lg)
-    ow.bits[:] = _sparse_bits(lg, 1e-6, 77 + LONG_WORLDS.index(lg))
+    ow.bits[:] = sparse_bits(lg, 1e-6, 77 + LONG_WORLDS.index(lg))
     ow.build_csdf()
     r, t = (rv.StateRender(lg, 64, 64) for _ in range(2))
     for c in (r, t):
@@ -76,10 +35,10 @@ def test_local_rebuild_equals_full_rebuild(rv, oracle, lg):
     for step, solid in enumerate((1, 0)):
         box = [(cx, cy, cz, cx + 1, cy + 1, cz + 1, solid)]
         r.world_edit(box)
-        _twin_edit(rv, t, lg, box)
+        twin_edit(rv, t, lg, box)
         ow.set_solid(cx, cy, cz, bool(solid))
         ow.build_csdf()
-        bits, csdf = _same_world(rv, r, t, (lg, solid))
+        bits, csdf = same_world(rv, r, t, (lg, solid))
         assert np.array_equal(bits, ow.bits) and np.array_equal(csdf, ow.csdf), (lg, solid)
         region, cells = rv.edit_region(lg, box)
         assert r.world_edit_info() == (step + 1, cells, False)
@@ -88,16 +47,16 @@ def test_local_rebuild_equals_full_rebuild(rv, oracle, lg):
     boxes = [(cx - 3, cy - 5, cz - 1, cx + 6, cy + 2, cz + 8, 1), (cx - 1, cy - 4, cz, cx + 3, cy + 1, cz + 7, 0),
              (cx + 5, cy - 5, cz + 7, cx + 9, cy - 4, cz + 9, 1)]
     r.world_edit(boxes)
-    _twin_edit(rv, t, lg, boxes)
-    ow.bits[:] = _edited(ow.bits, lg, boxes)
+    twin_edit(rv, t, lg, boxes)
+    ow.bits[:] = edited(ow.bits, lg, boxes)
     ow.build_csdf()
-    bits, csdf = _same_world(rv, r, t, (lg, "boxes"))
+    bits, csdf = same_world(rv, r, t, (lg, "boxes"))
     assert np.array_equal(bits, ow.bits) and np.array_equal(csdf, ow.csdf)
     assert r.world_edit_info() == (3, rv.edit_region(lg, boxes)[1], False)
     # setting what is already set changes nothing and counts as no edit
     r.world_edit(boxes[2:])
     assert r.world_edit_info() == (3, 0, False)
-    _same_world(rv, r, t, (lg, "repeat"))
+    same_world(rv, r, t, (lg, "repeat"))
     r.close()
     t.close()
 
@@ -113,7 +72,7 @@ def test_unaligned_overlapping_boxes_and_full_fallback(rv, oracle, oracle_world)
     base = oracle_world(7, 7, 7, gi_sweeps=0)
     assert np.array_equal(bits0, base.bits)
     # a coarse cell with all 8 voxels solid: clearing one of them leaves the cell solid
-    full = _voxels(bits0, lg).reshape(N // 2, 2, N // 2, 2, N // 2, 2).all(axis=(1, 3, 5))
+    full = voxels(bits0, lg).reshape(N // 2, 2, N // 2, 2, N // 2, 2).all(axis=(1, 3, 5))
     fz, fy, fx = (int(v[len(v) // 2]) for v in np.nonzero(full))
     boxes = [(5, 3, 7, 13, 9, 10, 1), (7, 4, 8, 11, 7, 9, 0)]
     for q in range(8):   # a one-voxel box at each world corner: bottom corners cleared, top corners set
@@ -122,18 +81,18 @@ def test_unaligned_overlapping_boxes_and_full_fallback(rv, oracle, oracle_world)
     boxes.append((2 * fx + 1, 2 * fy, 2 * fz + 1, 2 * fx + 2, 2 * fy + 1, 2 * fz + 2, 0))
     r.world_edit(boxes)
     assert r.world_edit_info()[2] is True   # 64^3 cells: every region covers the grid
-    _twin_edit(rv, t, lg, boxes)
+    twin_edit(rv, t, lg, boxes)
     ow = oracle.OracleWorld(*lg)
-    ow.bits[:] = _edited(bits0, lg, boxes)
+    ow.bits[:] = edited(bits0, lg, boxes)
     ow.build_csdf()
-    bits, csdf = _same_world(rv, r, t, "boxes")
+    bits, csdf = same_world(rv, r, t, "boxes")
     assert np.array_equal(bits, ow.bits) and np.array_equal(csdf, ow.csdf)
     assert r.world_edit_info()[0] == 1
     # a whole-world clear: the whole-grid build, an empty world
     clear = [(0, 0, 0, N, N, N, 0)]
     r.world_edit(clear)
-    _twin_edit(rv, t, lg, clear)
-    bits, csdf = _same_world(rv, r, t, "clear")
+    twin_edit(rv, t, lg, clear)
+    bits, csdf = same_world(rv, r, t, "clear")
     assert not bits.any() and (csdf == 64).all()
     assert r.world_edit_info() == (2, N ** 3 // 8, True)
     r.close()
@@ -162,10 +121,10 @@ def test_exits_follow_the_edit(rv, atlas, oracle, oracle_world):
              [(lx, N - 3, lz, lx + 1, N - 2, lz + 1, 1)]]         # ... and rise again, over the lowest column
     for boxes in steps:
         r.world_edit(boxes)
-        _twin_edit(rv, t, lg, boxes)
-        ow.bits[:] = _edited(ow.bits, lg, boxes)
+        twin_edit(rv, t, lg, boxes)
+        ow.bits[:] = edited(ow.bits, lg, boxes)
         ow.build_csdf()
-        bits, csdf = _same_world(rv, r, t, boxes)
+        bits, csdf = same_world(rv, r, t, boxes)
         assert np.array_equal(bits, ow.bits) and np.array_equal(csdf, ow.csdf)
         g, h = r.trace_rays(org, d, dist), t.trace_rays(org, d, dist)
         for f in g.dtype.names:
@@ -186,39 +145,6 @@ def test_exits_follow_the_edit(rv, atlas, oracle, oracle_world):
 
 
 # ---------------------------------------------------------------- 4. frames across an edit
-def _draw(r, d):
-    c = d.cam
-    r.draw_cuda(c.pos[:], c.forward[:], c.up[:], c.right[:], np.ctypeslib.as_array(d.vp),
-                np.ctypeslib.as_array(d.prev_vp), 0.0, d.time)
-
-
-def _same_frames(rv, r, t, what):
-    for k in (rv.RV_IMAGE_COLOR, rv.RV_IMAGE_MOTION, rv.RV_IMAGE_DEPTH):
-        assert np.array_equal(r.readback(k), t.readback(k)), (what, k)
-    assert np.array_equal(r.world_export(rv.RV_WORLD_GI), t.world_export(rv.RV_WORLD_GI)), what
-
-
-def _block_in_view(r, d, N):
-    """Boxes on a ray through the frame (the centre ray, or tilted down until it hits ground): the hit
-    block dug out, a block placed in the air 8 voxels before it.  Returns the boxes and the ray."""
-    c = d.cam
-    fo = np.asarray(c.forward[:], np.float64)
-    for tilt in (0.0, 0.15, 0.3, 0.45):
-        v = fo + tilt * np.array([0.0, -1.0, 0.0])
-        v /= np.linalg.norm(v)
-        ray = ([c.pos[:]], [v.astype(np.float32)], [0.0])
-        h = r.trace_rays(*ray)[0]
-        if h["hit"] and np.linalg.norm(np.asarray(h["pos"], np.float64) - np.asarray(c.pos[:])) > 16:
-            break
-    else:
-        raise AssertionError("no ground in view")
-    p = np.asarray(h["pos"], np.float64)
-    a = np.clip(np.floor(p).astype(int) - 1, 0, N - 3)
-    b = np.clip(np.floor(p - 8.0 * v).astype(int) - 1, 0, N - 3)
-    return [(int(a[0]), int(a[1]), int(a[2]), int(a[0]) + 3, int(a[1]) + 3, int(a[2]) + 3, 0),
-            (int(b[0]), int(b[1]), int(b[2]), int(b[0]) + 3, int(b[1]) + 3, int(b[2]) + 3, 1)], ray
-
-
 @pytest.mark.parametrize("mode,in_flight", [("draw", 1), ("seq", 1), ("group", 1), ("draw", 2), ("seq", 2)])
 def test_frames_across_an_edit(rv, atlas, mode, in_flight):
     """renderLoop's frames before and after an edit of a block in view: flow frames with the GI update
@@ -238,7 +164,7 @@ def test_frames_across_an_edit(rv, atlas, mode, in_flight):
         if mode == "group":
             c.set_frame_group(4)
             assert c.frame_group_effective() == 4
-    boxes, ray = _block_in_view(r, seq[n], 128)
+    boxes, ray = block_in_view(r, seq[n], 128)
     hit0 = r.trace_rays(*ray)[0]["pos"].copy()
 
     def run(k0):
@@ -246,18 +172,18 @@ def test_frames_across_an_edit(rv, atlas, mode, in_flight):
             for k in range(k0, k0 + n):
                 for c in (r, t):
                     c.update_gi_data()
-                    _draw(c, seq[k])
-                _same_frames(rv, r, t, k)
+                    draw(c, seq[k])
+                same_frames(rv, r, t, k)
         else:
             for c in (r, t):
                 c.render_frame_seq(seq[k0:k0 + n], next_desc=seq[k0 + n], flags=flags, gi_per_frame=True)
-            _same_frames(rv, r, t, k0)
+            same_frames(rv, r, t, k0)
     run(0)
     gi = r.world_export(rv.RV_WORLD_GI)
     r.world_edit(boxes)
-    _twin_edit(rv, t, lg, boxes)
+    twin_edit(rv, t, lg, boxes)
     assert r.world_edit_info()[0] == 1
-    _same_world(rv, r, t, "edit")
+    same_world(rv, r, t, "edit")
     assert np.array_equal(r.world_export(rv.RV_WORLD_GI), gi)   # the edit leaves the GI grid alone
     assert not np.array_equal(r.trace_rays(*ray)[0]["pos"], hit0)   # the placed block is on the ray
     run(n)
@@ -298,25 +224,6 @@ def test_edit_status_behaviour(rv):
 
 
 # ---------------------------------------------------------------- 6. two-rank loopback
-def _run_ranks(fns):
-    errs = [None] * len(fns)
-
-    def body(q):
-        try:
-            fns[q]()
-        except BaseException as e:   # noqa: BLE001 -- re-raised below
-            errs[q] = e
-    ts = [threading.Thread(target=body, args=(q,)) for q in range(len(fns))]
-    for th in ts:
-        th.start()
-    for th in ts:
-        th.join(timeout=300)
-        assert not th.is_alive(), "a rank thread hung"
-    for e in errs:
-        if e is not None:
-            raise e
-
-
 def test_two_rank_loop_with_an_edit_equals_one_rank(rv, atlas):
     """Both ranks of a tile-sharded loop apply the same edit between two calls: the gathered frame and
     every rank's GI grid equal one context rendering whole frames one at a time with the same edit."""
@@ -338,13 +245,13 @@ def test_two_rank_loop_with_an_edit_equals_one_rank(rv, atlas):
     for q, c in enumerate(rs):
         c.set_tile_shard(32, q, N)
         comms.append(rv.Comm.loopback(c, group, q))
-    boxes, _ = _block_in_view(ref, seq[4], 128)
+    boxes, _ = block_in_view(ref, seq[4], 128)
     for a, b in ((0, 4), (4, 8)):
         if a:
             for c in rs + [ref]:
                 c.world_edit(boxes)
-        _run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b], flags=flags, gi_per_frame=True,
-                                                       comm=comms[q]) for q in range(N)])
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b], flags=flags, gi_per_frame=True,
+                                                      comm=comms[q]) for q in range(N)])
         for m in comms:
             m.wait(60000)
         for k in range(a, b):

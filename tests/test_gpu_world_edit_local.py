@@ -16,22 +16,15 @@ import numpy as np
 import pytest
 
 from conftest import random_rays
-from test_gpu_gi_relight import expect_relight
-from test_gpu_world_edit import (_block_in_view, _draw, _edited, _run_ranks, _same_frames, _same_world, _sparse_bits,
-                                 _twin_edit, _voxels)
+from gpu_world import (block_in_view, cells, draw, edited, oracle_of, pack, run_ranks, rv, same_frames, same_world,
+                       sparse_bits, twin_edit, voxels)
+from np_world import expect_relight
 
 pytestmark = pytest.mark.gpu
 
 T_LG = (9, 7, 7)
 S_SEED = {(8, 8, 8): 31, (7, 9, 7): 32, (7, 7, 9): 33}
 W, H = 160, 96
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +43,7 @@ def sparse(oracle):
     def make(lg):
         if lg not in _SPARSE:
             ow = oracle.OracleWorld(*lg)
-            ow.bits[:] = _sparse_bits(lg, 2e-5, S_SEED[lg])
+            ow.bits[:] = sparse_bits(lg, 2e-5, S_SEED[lg])
             ow.build_csdf()
             _SPARSE[lg] = (ow.bits.copy(), ow.csdf.copy())
         return _SPARSE[lg]
@@ -58,24 +51,6 @@ def sparse(oracle):
 
 
 # ---------------------------------------------------------------- helpers
-def _cells(lg):
-    return tuple(1 << (l - 1) for l in lg)
-
-
-def _pack(vox):
-    return np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
-
-
-def _oracle_of(oracle, lg, bits, csdf=None, atlas=None):
-    ow = oracle.OracleWorld(*lg, atlas=atlas)
-    ow.bits[:] = bits
-    if csdf is None:
-        ow.build_csdf()
-    else:
-        ow.csdf[:] = csdf
-    return ow
-
-
 def _pair(rv, lg, bits=None, w=64, h=64, **kw):
     """A context and its twin holding the same world: the generated one, or these bits."""
     r, t = (rv.StateRender(lg, w, h, **kw) for _ in range(2))
@@ -89,10 +64,10 @@ def _pair(rv, lg, bits=None, w=64, h=64, **kw):
 
 
 def _assert_local(rv, r, lg, boxes, n):
-    region, cells = rv.edit_region(lg, boxes)
-    SX, SY, SZ = _cells(lg)
-    assert 0 < cells < SX * SY * SZ
-    assert r.world_edit_info() == (n, cells, False), (n, cells, r.world_edit_info())
+    region, ncells = rv.edit_region(lg, boxes)
+    SX, SY, SZ = cells(lg)
+    assert 0 < ncells < SX * SY * SZ
+    assert r.world_edit_info() == (n, ncells, False), (n, ncells, r.world_edit_info())
     return region
 
 
@@ -100,12 +75,12 @@ def _halo_matters(oracle, ow, lg, region):
     """CPU only.  The CSDF inside the region F of a world that keeps only F's own voxels differs from the
     real one inside F, and F holds many distinct values: the bytes a local rebuild writes depend on what
     its halo boxes (solid, dx, dy beyond F) hold, so a wrong stride, clip or halo there shows."""
-    SX, SY, SZ = _cells(lg)
+    SX, SY, SZ = cells(lg)
     x0, x1, y0, y1, z0, z1 = region
     vox = ow.voxels()
     cut = np.zeros_like(vox)
     cut[2 * z0:2 * z1, 2 * y0:2 * y1, 2 * x0:2 * x1] = vox[2 * z0:2 * z1, 2 * y0:2 * y1, 2 * x0:2 * x1]
-    alone = _oracle_of(oracle, lg, _pack(cut))
+    alone = oracle_of(oracle, lg, pack(cut))
     F = (slice(z0, z1), slice(y0, y1), slice(x0, x1))
     whole = ow.csdf.reshape(SZ, SY, SX)[F]
     differing = int((alone.csdf.reshape(SZ, SY, SX)[F] != whole).sum())
@@ -119,14 +94,14 @@ def _edit_steps(rv, oracle, r, t, ow, lg, steps, full=(), want_region=None):
     """Each step's boxes through world_edit on r, the host edit + csdf_build on t and the oracle; bits and
     CSDF of the three compared over the whole grid.  `full` lists the steps (from 1) that must report the
     whole-grid build; every other step must report the local one.  Returns the CSDF bytes each step changed."""
-    SX, SY, SZ = _cells(lg)
+    SX, SY, SZ = cells(lg)
     out = []
     checked = False
     for n, boxes in enumerate(steps, 1):
         prev = ow.csdf.copy()
         r.world_edit(boxes)
-        _twin_edit(rv, t, lg, boxes)
-        ow.bits[:] = _edited(ow.bits, lg, boxes)
+        twin_edit(rv, t, lg, boxes)
+        ow.bits[:] = edited(ow.bits, lg, boxes)
         ow.build_csdf()
         if n in full:
             assert r.world_edit_info() == (n, SX * SY * SZ, True), (n, r.world_edit_info())
@@ -134,7 +109,7 @@ def _edit_steps(rv, oracle, r, t, ow, lg, steps, full=(), want_region=None):
             region = _assert_local(rv, r, lg, boxes, n)
             if n == 1 and want_region is not None:
                 assert region == want_region, (region, want_region)
-        bits, csdf = _same_world(rv, r, t, (lg, n))
+        bits, csdf = same_world(rv, r, t, (lg, n))
         assert np.array_equal(bits, ow.bits) and np.array_equal(csdf, ow.csdf), (lg, n)
         changed = int((ow.csdf != prev).sum())
         what = boxes if len(boxes) < 4 else f"{len(boxes)} boxes"
@@ -175,7 +150,7 @@ def test_local_rebuild_in_the_terrain(rv, oracle, terrain, p, span):
     r, t = _pair(rv, lg)
     assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), terrain[0])
     assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), terrain[1])
-    ow = _oracle_of(oracle, lg, *terrain)
+    ow = oracle_of(oracle, lg, *terrain)
     z = 61
     col = ow.voxels()[z + 1, :, p + 1]
     y = min(int(np.nonzero(col)[0].max()) + 1, 124)   # on the ground of the middle column
@@ -190,7 +165,7 @@ def test_local_rebuild_along_y_and_z(rv, oracle, sparse, lg, p, span):
     bits0, csdf0 = sparse(lg)
     r, t = _pair(rv, lg, bits0)
     assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), csdf0)
-    ow = _oracle_of(oracle, lg, bits0, csdf0)
+    ow = oracle_of(oracle, lg, bits0, csdf0)
     at = (61, p, 70) if lg[1] == 9 else (61, 70, p)
     want = (0, 64) + span + (0, 64) if lg[1] == 9 else (0, 64, 0, 64) + span
     _edit_steps(rv, oracle, r, t, ow, lg, _set_then_clear(*at), want_region=want)
@@ -218,7 +193,7 @@ def test_local_rebuild_on_three_axes(rv, oracle, sparse, at, region):
     bits0, csdf0 = sparse(lg)
     r, t = _pair(rv, lg, bits0)
     assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), csdf0)
-    ow = _oracle_of(oracle, lg, bits0, csdf0)
+    ow = oracle_of(oracle, lg, bits0, csdf0)
     _edit_steps(rv, oracle, r, t, ow, lg, _set_then_clear(*at), full=(1,) if region is None else (),
                 want_region=region)
     r.close()
@@ -235,22 +210,22 @@ def test_longest_edit_list_in_order(rv, oracle, terrain):
     for _ in range(n):   # box by box: the origin, the sides of 1 to 11 voxels, solid or not
         o, s, k = rng.integers((200, 60, 50), (240, 100, 90)), rng.integers(1, 12, 3), rng.integers(0, 2)
         boxes.append(tuple(int(v) for v in (*o, *(o + s), k)))
-    want = _edited(terrain[0], lg, boxes)
-    changed = int((_voxels(want, lg) != _voxels(terrain[0], lg)).sum())
-    reverse = _edited(terrain[0], lg, boxes[::-1])
-    by_kind = _edited(terrain[0], lg, [b for b in boxes if not b[6]] + [b for b in boxes if b[6]])
-    d_rev = int((_voxels(reverse, lg) != _voxels(want, lg)).sum())
-    d_kind = int((_voxels(by_kind, lg) != _voxels(want, lg)).sum())
+    want = edited(terrain[0], lg, boxes)
+    changed = int((voxels(want, lg) != voxels(terrain[0], lg)).sum())
+    reverse = edited(terrain[0], lg, boxes[::-1])
+    by_kind = edited(terrain[0], lg, [b for b in boxes if not b[6]] + [b for b in boxes if b[6]])
+    d_rev = int((voxels(reverse, lg) != voxels(want, lg)).sum())
+    d_kind = int((voxels(by_kind, lg) != voxels(want, lg)).sum())
     print(f"{n} boxes change {changed} voxels; {d_rev} differ in reverse order, {d_kind} with the clears first")
     assert changed > 0 and d_rev > 0 and d_kind > 0   # the order of the list matters
     r, t = _pair(rv, lg)
-    ow = _oracle_of(oracle, lg, *terrain)
+    ow = oracle_of(oracle, lg, *terrain)
     _edit_steps(rv, oracle, r, t, ow, lg, [boxes])
     assert np.array_equal(ow.bits, want)
     # the same list again changes no voxel: no rebuild, not an edit
     r.world_edit(boxes)
     assert r.world_edit_info() == (1, 0, False)
-    _same_world(rv, r, t, "repeat")
+    same_world(rv, r, t, "repeat")
     r.close()
     t.close()
 
@@ -275,10 +250,10 @@ def test_exits_follow_a_local_edit(rv, atlas, oracle, terrain):
     lg = T_LG
     X, Y, Z = (1 << l for l in lg)
     flags = rv.RV_FLAGS_REFERENCE
-    vox = _voxels(terrain[0], lg)
+    vox = voxels(terrain[0], lg)
     vox[:, 90:, :] = False            # the terrain reaches row 127: cut it, so the sky exit has room to move
     assert vox[:, 89, :].any()
-    ow = _oracle_of(oracle, lg, _pack(vox), atlas=atlas)
+    ow = oracle_of(oracle, lg, pack(vox), atlas=atlas)
     r, t = _frame_pair(rv, atlas, lg, ow.bits)
     assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), ow.csdf)
     ow.gi[:] = r.world_export(rv.RV_WORLD_GI)
@@ -303,11 +278,11 @@ def test_exits_follow_a_local_edit(rv, atlas, oracle, terrain):
     for n, boxes in enumerate(steps, 1):
         prev = ow.csdf.copy()
         r.world_edit(boxes)
-        _twin_edit(rv, t, lg, boxes)
-        ow.bits[:] = _edited(ow.bits, lg, boxes)
+        twin_edit(rv, t, lg, boxes)
+        ow.bits[:] = edited(ow.bits, lg, boxes)
         ow.build_csdf()
         _assert_local(rv, r, lg, boxes, n)
-        bits, csdf = _same_world(rv, r, t, boxes)
+        bits, csdf = same_world(rv, r, t, boxes)
         assert np.array_equal(bits, ow.bits) and np.array_equal(csdf, ow.csdf)
         print(f"{boxes}: local, {int((csdf != prev).sum())} CSDF bytes change")
         assert (csdf != prev).any()
@@ -345,7 +320,7 @@ def test_frames_across_a_local_edit(rv, atlas, mode, in_flight):
         if mode == "group":
             c.set_frame_group(4)
             assert c.frame_group_effective() == 4
-    boxes, ray = _block_in_view(r, seq[n], np.array([1 << l for l in lg]))
+    boxes, ray = block_in_view(r, seq[n], np.array([1 << l for l in lg]))
     hit0 = r.trace_rays(*ray)[0]["pos"].copy()
 
     def run(k0):
@@ -353,18 +328,18 @@ def test_frames_across_a_local_edit(rv, atlas, mode, in_flight):
             for k in range(k0, k0 + n):
                 for c in (r, t):
                     c.update_gi_data()
-                    _draw(c, seq[k])
-                _same_frames(rv, r, t, k)
+                    draw(c, seq[k])
+                same_frames(rv, r, t, k)
         else:
             for c in (r, t):
                 c.render_frame_seq(seq[k0:k0 + n], next_desc=seq[k0 + n], flags=flags, gi_per_frame=True)
-            _same_frames(rv, r, t, k0)
+            same_frames(rv, r, t, k0)
     run(0)
     gi = r.world_export(rv.RV_WORLD_GI)
     r.world_edit(boxes)
-    _twin_edit(rv, t, lg, boxes)
+    twin_edit(rv, t, lg, boxes)
     _assert_local(rv, r, lg, boxes, 1)
-    _same_world(rv, r, t, "edit")
+    same_world(rv, r, t, "edit")
     assert np.array_equal(r.world_export(rv.RV_WORLD_GI), gi)   # the edit leaves the GI grid alone
     assert not np.array_equal(r.trace_rays(*ray)[0]["pos"], hit0)   # the placed block is on the ray
     run(n)
@@ -381,10 +356,10 @@ def _edited_terrain(rv, oracle, atlas, terrain, r):
     from rvgrt_amd.configs import TEST_POSES_128, camera_path
     lg = T_LG
     seq = camera_path(TEST_POSES_128["P0"], W, H, 1, pan=0.01, ref_compat=True)
-    boxes, _ = _block_in_view(r, seq[0], np.array([1 << l for l in lg]))
+    boxes, _ = block_in_view(r, seq[0], np.array([1 << l for l in lg]))
     r.world_edit(boxes)
     _assert_local(rv, r, lg, boxes, 1)
-    ow = _oracle_of(oracle, lg, _edited(terrain[0], lg, boxes), atlas=atlas)
+    ow = oracle_of(oracle, lg, edited(terrain[0], lg, boxes), atlas=atlas)
     assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), ow.bits)
     assert np.array_equal(r.world_export(rv.RV_WORLD_CSDF), ow.csdf)
     assert not np.array_equal(ow.csdf, terrain[1])
@@ -450,7 +425,7 @@ def test_two_rank_loop_with_a_local_edit_and_a_relight(rv, atlas):
     for q, c in enumerate(rs):
         c.set_tile_shard(32, q, N)
         comms.append(rv.Comm.loopback(c, group, q))
-    boxes, _ = _block_in_view(ref, seq[4], np.array([1 << l for l in lg]))
+    boxes, _ = block_in_view(ref, seq[4], np.array([1 << l for l in lg]))
     box = rv.relight_box(lg, boxes, margin=4)
     for a, b in ((0, 4), (4, 8)):
         if a:
@@ -463,8 +438,8 @@ def test_two_rank_loop_with_a_local_edit_and_a_relight(rv, atlas):
             assert not np.array_equal(relit, before)
             for q, c in enumerate(rs):
                 assert np.array_equal(c.world_export(rv.RV_WORLD_GI), relit), q
-        _run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b], flags=flags, gi_per_frame=True,
-                                                       comm=comms[q]) for q in range(N)])
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b], flags=flags, gi_per_frame=True,
+                                                      comm=comms[q]) for q in range(N)])
         for m in comms:
             m.wait(60000)
         for k in range(a, b):
@@ -529,7 +504,7 @@ def test_scratch_above_the_kept_size_is_freed_and_reserved_again(rv):
         _assert_local(rv, r, lg, [box], n)
         t.world_import(rv.RV_WORLD_BITS, bits)
         t.csdf_build()
-        got, csdf = _same_world(rv, r, t, box)
+        got, csdf = same_world(rv, r, t, box)
         assert np.array_equal(got, bits)
         changed = int((csdf != prev_csdf).sum())
         print(f"{box}: local, {changed} CSDF bytes change")

@@ -9,60 +9,14 @@ comparison is bit-exact."""
 import numpy as np
 import pytest
 
+from gpu_world import dims, draw, generated, gi, rv, shifted, sparse_bits, step, sun, tables, voxels, world
 import np_exits as E
-import test_world_scroll_region as R
-from test_world_persist_map import column_bits
+import np_world as R
+from np_world import column_bits
 
 pytestmark = pytest.mark.gpu
 
 W, H = 320, 192
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-@pytest.fixture(scope="module")
-def sun(oracle):
-    return np.ascontiguousarray(oracle.sun_dir(), np.float32)
-
-
-def _dims(lg):
-    return tuple(1 << l for l in lg)
-
-
-def _voxels(bits, lg):
-    X, Y, Z = _dims(lg)
-    return np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(Z, Y, X).astype(bool)
-
-
-def _world(rv, r):
-    return r.world_export(rv.RV_WORLD_BITS), r.world_export(rv.RV_WORLD_CSDF)
-
-
-def _tables(rv, r):
-    return (r.world_top_info(), r.world_export(rv.RV_WORLD_COLTOP), r.world_export(rv.RV_WORLD_HORIZON),
-            r.world_export(rv.RV_WORLD_DTOP))
-
-
-def _gi(rv, r, lg):
-    X, Y, Z = _dims(lg)
-    return r.world_export(rv.RV_WORLD_GI).view(np.uint32).reshape(Z // 4, Y // 4, X // 4)
-
-
-def _generated(oracle, lg, origin):
-    """The oracle's generated window at `origin` (bits), built once per window."""
-    key = ("persist", lg, origin)
-    if key not in R._TERRAIN:
-        R._TERRAIN[key] = oracle.OracleWorld(*lg, ox=origin[0], oz=origin[1]).fill().bits.copy()
-    return R._TERRAIN[key]
-
-
-def _step(axis, d):
-    return (d, 0) if axis == 0 else (0, d)
 
 
 def _boxes(bx, bz, variant=0):
@@ -82,7 +36,7 @@ def _info(r, *names):
 def _check_world(rv, oracle, sun, r, lg, want_bits, label):
     """Bits as expected; the CSDF is the oracle's build of them; ytop, column tops, skip table and horizon
     are those of a twin that imports the bits and builds the CSDF, and pass the numpy restatement."""
-    bits, csdf = _world(rv, r)
+    bits, csdf = world(rv, r)
     assert np.array_equal(bits, want_bits), (label, "bits")
     ow = oracle.OracleWorld(*lg)
     ow.bits[:] = bits
@@ -91,20 +45,20 @@ def _check_world(rv, oracle, sun, r, lg, want_bits, label):
     t = rv.StateRender(lg, 64, 64)
     t.world_import(rv.RV_WORLD_BITS, bits)
     t.csdf_build()
-    tabs, twin = _tables(rv, r), _tables(rv, t)
+    tabs, twin = tables(rv, r), tables(rv, t)
     assert np.array_equal(t.world_export(rv.RV_WORLD_CSDF), csdf), (label, "twin csdf")
     t.close()
     assert tabs[0] == twin[0], (label, "ytop")
     for a, b in zip(tabs[1:], twin[1:]):
         assert np.array_equal(a, b), (label, "tables")
-    E.check_tables(E.reference(_voxels(bits, lg), sun), *tabs, label)
+    E.check_tables(E.reference(voxels(bits, lg), sun), *tabs, label)
     return ow
 
 
 # ---------------------------------------------------------------- 1. the gather kernel
 @pytest.mark.parametrize("lg", [(9, 7, 7), (7, 7, 9), (6, 8, 6), (6, 10, 6)])
 def test_columns_read(rv, lg):
-    X, Y, Z = _dims(lg)
+    X, Y, Z = dims(lg)
     nbx, nbz = X // 8, Z // 8
     r = rv.StateRender(lg, 64, 64, seed=(16, -40))
     with pytest.raises(rv.RvError, match="RV_ERR_STATE"):
@@ -115,7 +69,7 @@ def test_columns_read(rv, lg):
     cols += [(int(rng.integers(nbx)), int(rng.integers(nbz))) for _ in range(70 - len(cols))]
     got = r.world_columns_read(cols)
     assert got.shape == (70, 2 * Y)
-    vox = _voxels(r.world_export(rv.RV_WORLD_BITS), lg)
+    vox = voxels(r.world_export(rv.RV_WORLD_BITS), lg)
     some = False
     for (bx, bz), g in zip(cols, got):
         want = column_bits(vox, bx, bz)
@@ -140,27 +94,27 @@ def test_away_and_back(rv, oracle, sun, lg, axis, d, col):
     """Without persistence the generated terrain returns in place of the edited column, so the bits
     comparison after the way back fails on a library that lacks it."""
     origin = (16, -40)
-    G = tuple(v // 4 for v in _dims(lg))
+    G = tuple(v // 4 for v in dims(lg))
     r = rv.StateRender(lg, 64, 64, seed=origin)
     r.world_persist(True)
     r.world_build()
     assert _info(r, "on", "dirty_columns", "stored_columns") == (True, 0, 0)
     r.world_edit(_boxes(*col))
     bits0 = r.world_export(rv.RV_WORLD_BITS)
-    gen = _generated(oracle, lg, origin)
-    mine, theirs = column_bits(_voxels(bits0, lg), *col), column_bits(_voxels(gen, lg), *col)
+    gen = generated(oracle, lg, origin)
+    mine, theirs = column_bits(voxels(bits0, lg), *col), column_bits(voxels(gen, lg), *col)
     assert not np.array_equal(mine, theirs)      # the edit changed the column: the test cannot be vacuous
     assert _info(r, "dirty_columns", "stored_columns") == (1, 0)
 
-    r.world_scroll(*_step(axis, d))              # the column leaves
+    r.world_scroll(*step(axis, d))              # the column leaves
     assert _info(r, "dirty_columns", "stored_columns", "stored_bytes", "captured_total", "restored_total") == \
-        (0, 1, 8 * _dims(lg)[1], 1, 0)
+        (0, 1, 8 * dims(lg)[1], 1, 0)
     key = (origin[0] + 8 * col[0], origin[1] + 8 * col[1])
     assert r.world_store_list().tolist() == [list(key)]
     assert np.array_equal(r.world_store_get(*key), mine)
-    g0 = _gi(rv, r, lg)
+    g0 = gi(rv, r, lg)
 
-    r.world_scroll(*_step(axis, -d))             # ... and returns
+    r.world_scroll(*step(axis, -d))             # ... and returns
     assert r.world_scroll_info()[3] == origin and not r.world_scroll_info()[2]
     ow = _check_world(rv, oracle, sun, r, lg, bits0, f"{lg} back")
     assert np.array_equal(r.world_columns_read([col])[0], mine)
@@ -168,7 +122,7 @@ def test_away_and_back(rv, oracle, sun, lg, axis, d, col):
     assert len(r.world_store_list()) == 0
     # the GI grid of the step back (by -d): retained cells moved, entering cells the oracle's gi_init in the
     # final world -- the restored column's among them
-    g1 = _gi(rv, r, lg)
+    g1 = gi(rv, r, lg)
     g, ax = -d // 4, 2 - axis
     new, old, ent = ([slice(None)] * 3 for _ in range(3))
     new[ax] = slice(0, G[axis] - g) if g > 0 else slice(-g, G[axis])
@@ -189,7 +143,7 @@ def test_diagonal(rv, oracle, sun):
     r.world_build()
     r.world_edit(_boxes(*col))
     bits0 = r.world_export(rv.RV_WORLD_BITS)
-    assert not np.array_equal(bits0, _generated(oracle, lg, origin))
+    assert not np.array_equal(bits0, generated(oracle, lg, origin))
     r.world_scroll(16, 8)
     assert _info(r, "dirty_columns", "stored_columns") == (0, 1)
     assert r.world_store_list().tolist() == [list(origin)]
@@ -210,7 +164,7 @@ def test_everything_leaves(rv, oracle, sun, dx, dz):
     bits0 = r.world_export(rv.RV_WORLD_BITS)
     assert _info(r, "dirty_columns", "stored_columns") == (2, 0)
     r.world_scroll(dx, dz)
-    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), _generated(oracle, lg, (dx, dz)))
+    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), generated(oracle, lg, (dx, dz)))
     assert _info(r, "dirty_columns", "stored_columns") == (0, 2)
     r.world_scroll(-dx, -dz)
     _check_world(rv, oracle, sun, r, lg, bits0, "everything leaves")
@@ -221,7 +175,7 @@ def test_everything_leaves(rv, oracle, sun, dx, dz):
 @pytest.mark.parametrize("lg", [(6, 10, 6), (7, 4, 7)])
 def test_tall_and_flat_columns(rv, oracle, lg):
     """Columns of 128 bricks (the kernels stage 64 at a time: two passes) and of 2 (eight lanes at work)."""
-    X, Y, Z = _dims(lg)
+    X, Y, Z = dims(lg)
     r = rv.StateRender(lg, 64, 64, seed=(8, 8))
     r.world_persist(True)
     r.world_build()
@@ -229,17 +183,17 @@ def test_tall_and_flat_columns(rv, oracle, lg):
     r.world_edit([b for bx, bz in cols for b in
                   ((8 * bx + 1, Y // 2, 8 * bz + 1, 8 * bx + 7, Y - 2, 8 * bz + 7, 1),
                    (8 * bx + 2, 0, 8 * bz + 2, 8 * bx + 6, Y // 2 + 4, 8 * bz + 6, 0))])
-    bits0, csdf0 = _world(rv, r)
-    vox = _voxels(bits0, lg)
+    bits0, csdf0 = world(rv, r)
+    vox = voxels(bits0, lg)
     read = r.world_columns_read(cols)
     for (bx, bz), got in zip(cols, read):
         assert np.array_equal(got, column_bits(vox, bx, bz)), (lg, bx, bz)
-    assert not np.array_equal(bits0, _generated(oracle, lg, (8, 8)))
+    assert not np.array_equal(bits0, generated(oracle, lg, (8, 8)))
     r.world_scroll(X, -Z)
     assert _info(r, "dirty_columns", "stored_columns") == (0, 3)
-    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), _generated(oracle, lg, (8 + X, 8 - Z)))
+    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), generated(oracle, lg, (8 + X, 8 - Z)))
     r.world_scroll(-X, Z)
-    bits, csdf = _world(rv, r)
+    bits, csdf = world(rv, r)
     assert np.array_equal(bits, bits0) and np.array_equal(csdf, csdf0)
     assert _info(r, "dirty_columns", "stored_columns") == (3, 0)
     r.close()
@@ -248,23 +202,23 @@ def test_tall_and_flat_columns(rv, oracle, lg):
 # ---------------------------------------------------------------- 5. an imported world
 def test_imported_world(rv, oracle):
     lg = (10, 6, 6)
-    X, Y, Z = _dims(lg)
+    X, Y, Z = dims(lg)
     r = rv.StateRender(lg, 64, 64, seed=R.ORIGIN)
     r.world_persist(True)
-    imported = R.sparse_bits(1 << sum(lg), 2e-5, 31)
+    imported = sparse_bits(lg, 2e-5, 31)
     r.world_import(rv.RV_WORLD_BITS, imported)
     r.csdf_build()
     assert _info(r, "dirty_columns") == (X // 8 * (Z // 8),)
-    bits0, csdf0 = _world(rv, r)
+    bits0, csdf0 = world(rv, r)
     assert np.array_equal(bits0, imported)
     # what the walk leaves without persistence: generated terrain in the left-hand 40 voxels
-    gen = _voxels(_generated(oracle, lg, R.ORIGIN), lg)
-    assert not np.array_equal(gen[:, :, :40], _voxels(imported, lg)[:, :, :40])
+    gen = voxels(generated(oracle, lg, R.ORIGIN), lg)
+    assert not np.array_equal(gen[:, :, :40], voxels(imported, lg)[:, :, :40])
     for _ in range(5):
         r.world_scroll(8, 0)
     assert _info(r, "stored_columns", "captured_total") == (5 * (Z // 8), 5 * (Z // 8))
     r.world_scroll(-40, 0)
-    bits, csdf = _world(rv, r)
+    bits, csdf = world(rv, r)
     assert np.array_equal(bits, bits0) and np.array_equal(csdf, csdf0)
     # the five generated slabs that left on the way back were never dirty
     assert _info(r, "dirty_columns", "stored_columns", "restored_total") == (X // 8 * (Z // 8), 0, 5 * (Z // 8))
@@ -291,7 +245,7 @@ def test_newer_wins_and_noop_marks_nothing(rv, oracle):
     assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), second)
     assert _info(r, "dirty_columns", "stored_columns", "restored_total") == (1, 0, 2)
     # an edit that changes no voxel, in a column that is not dirty: a box that re-writes what is there
-    vox = _voxels(second, lg)
+    vox = voxels(second, lg)
     box = next(b for b in ((64, 120, 64, 72, 128, 72), (64, 0, 64, 72, 8, 72))
                if vox[b[2]:b[5], b[1]:b[4], b[0]:b[3]].all() or not vox[b[2]:b[5], b[1]:b[4], b[0]:b[3]].any())
     solid = int(vox[box[2]:box[5], box[1]:box[4], box[0]:box[3]].all())
@@ -316,7 +270,7 @@ def test_off_forgets_the_edit(rv, oracle, toggle):
         r.world_persist(True)
         r.world_persist(False)
     r.world_edit(_boxes(*col))
-    gen = _generated(oracle, lg, origin)
+    gen = generated(oracle, lg, origin)
     assert not np.array_equal(r.world_export(rv.RV_WORLD_BITS), gen)
     assert r.world_persist_info() == zeros
     r.world_scroll(16, 0)
@@ -331,7 +285,7 @@ def test_off_forgets_the_edit(rv, oracle, toggle):
 # ---------------------------------------------------------------- 8. save and load
 def test_save_and_load(rv, oracle, sun):
     lg, origin = (7, 7, 7), (24, -16)
-    Y = _dims(lg)[1]
+    Y = dims(lg)[1]
     a = rv.StateRender(lg, 64, 64, seed=origin)
     a.world_persist(True)
     a.world_build()
@@ -367,11 +321,11 @@ def test_save_and_load(rv, oracle, sun):
 
     a.world_scroll(-16, 0)                       # back to the origin
     assert _info(a, "dirty_columns", "stored_columns") == (3, 2)
-    bits, csdf = _world(rv, a)
-    assert not np.array_equal(bits, _generated(oracle, lg, origin))
+    bits, csdf = world(rv, a)
+    assert not np.array_equal(bits, generated(oracle, lg, origin))
     _check_world(rv, oracle, sun, b, lg, bits, "loaded")
     assert np.array_equal(b.world_export(rv.RV_WORLD_CSDF), csdf)
-    ta, tb = _tables(rv, a), _tables(rv, b)
+    ta, tb = tables(rv, a), tables(rv, b)
     assert ta[0] == tb[0] and all(np.array_equal(x, y) for x, y in zip(ta[1:], tb[1:]))
     # rv_world_store_clear empties both
     a.world_store_clear()
@@ -381,17 +335,6 @@ def test_save_and_load(rv, oracle, sun):
 
 
 # ---------------------------------------------------------------- 9. frames and work computed ahead
-def _draw(r, d):
-    c = d.cam
-    r.draw_cuda(c.pos[:], c.forward[:], c.up[:], c.right[:], np.ctypeslib.as_array(d.vp),
-                np.ctypeslib.as_array(d.prev_vp), 0.0, d.time)
-
-
-def _shifted(rv, d, dx, dz):
-    cam, vp, pvp = rv.scroll_view(dx, dz, d.cam, np.ctypeslib.as_array(d.vp), np.ctypeslib.as_array(d.prev_vp))
-    return rv.frame_desc(cam, vp, pvp, d.time, d.jitter_x, d.jitter_y)
-
-
 def test_frames_across_a_return(rv, oracle, atlas):
     """Flow frames (whose launch computes the next GI update ahead) before and after the scroll that brings
     edited columns back into view.  t: nothing computed ahead, the world handed over through world_import.
@@ -416,11 +359,11 @@ def test_frames_across_a_return(rv, oracle, atlas):
         c.world_scroll(dx, dz)
     # stored: the columns under x < 16 or z < 16; still dirty: the interior's
     assert _info(r, "dirty_columns", "stored_columns") == (14 * 14, 2 * 16 + 2 * 14)
-    away = [_shifted(rv, d, dx, dz) for d in seq[:2]]
+    away = [shifted(rv, d, dx, dz) for d in seq[:2]]
     for c in (r, t, g):
         for d in away:
             c.update_gi_data()
-            _draw(c, d)
+            draw(c, d)
     assert r.flow_info()[0] and r.flow_info()[1] == 2
     for c in (r, g):
         c.world_scroll(-dx, -dz)
@@ -431,7 +374,7 @@ def test_frames_across_a_return(rv, oracle, atlas):
     t.world_import(rv.RV_WORLD_GI, r.world_export(rv.RV_WORLD_GI))
     for c in (r, t, g):
         c.update_gi_data()
-        _draw(c, seq[2])
+        draw(c, seq[2])
     for k in (rv.RV_IMAGE_COLOR, rv.RV_IMAGE_MOTION, rv.RV_IMAGE_DEPTH):
         assert np.array_equal(r.readback(k), t.readback(k)), k
     assert np.array_equal(r.world_export(rv.RV_WORLD_GI), t.world_export(rv.RV_WORLD_GI))

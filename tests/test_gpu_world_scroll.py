@@ -6,70 +6,17 @@ the oracle (OracleWorld at the new origin; build_csdf of the expected bits;
 gi_init / gi_update), the numpy exit tables of tests/np_exits.py and twin
 contexts (built at the new seed, or fed the expected world through
 world_import).  Every comparison is bit-exact."""
-import threading
-
 import numpy as np
 import pytest
 
+from gpu_world import (ctx128, dims, draw, generated, gi, run_ranks, rv, same_frames, same_tables, shifted, sparse_bits,
+                       step, sun, tables, voxels, world)
 import np_exits as E
-import test_world_scroll_region as R
+import np_world as R
 
 pytestmark = pytest.mark.gpu
 
 W, H = 320, 192
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-@pytest.fixture(scope="module")
-def sun(oracle):
-    return np.ascontiguousarray(oracle.sun_dir(), np.float32)
-
-
-def _dims(lg):
-    return tuple(1 << l for l in lg)
-
-
-def _voxels(bits, lg):
-    X, Y, Z = _dims(lg)
-    return np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(Z, Y, X).astype(bool)
-
-
-def _world(rv, r):
-    return r.world_export(rv.RV_WORLD_BITS), r.world_export(rv.RV_WORLD_CSDF)
-
-
-def _tables(rv, r):
-    return (r.world_top_info(), r.world_export(rv.RV_WORLD_COLTOP), r.world_export(rv.RV_WORLD_HORIZON),
-            r.world_export(rv.RV_WORLD_DTOP))
-
-
-def _same_tables(a, b, what):
-    assert a[0] == b[0], what
-    for x, y in zip(a[1:], b[1:]):
-        assert np.array_equal(x, y), what
-
-
-def _gi(rv, r):
-    return r.world_export(rv.RV_WORLD_GI).view(np.uint32)
-
-
-def _generated(oracle, lg, origin):
-    """The oracle's window at `origin`: (bits, csdf), built once per window."""
-    key = ("gen", lg, origin)
-    if key not in R._TERRAIN:
-        ow = oracle.OracleWorld(*lg, ox=origin[0], oz=origin[1]).fill().build_csdf()
-        R._TERRAIN[key] = (ow.bits.copy(), ow.csdf.copy())
-    return R._TERRAIN[key]
-
-
-def _step(axis, d):
-    return (d, 0) if axis == 0 else (0, d)
 
 
 def _entering(lg, axis, d, arr, cell):
@@ -88,16 +35,16 @@ def _box(arr, b):
 # ---------------------------------------------------------------- 1. generated terrain
 @pytest.mark.parametrize("lg,axis", [((9, 7, 7), 0), ((7, 7, 9), 2)])
 def test_generated_terrain(rv, oracle, sun, lg, axis):
-    S = tuple(d // 2 for d in _dims(lg))
+    S = tuple(d // 2 for d in dims(lg))
     origin = [16, -40]
     r = rv.StateRender(lg, 64, 64, seed=tuple(origin))
     r.world_build()
     assert r.world_scroll_info() == (0, 0, False, tuple(origin))
     for n, d in enumerate((8, -24, 64), 1):
-        r.world_scroll(*_step(axis, d))
+        r.world_scroll(*step(axis, d))
         origin[0 if axis == 0 else 1] += d
-        bits, csdf = _world(rv, r)
-        want_bits, want_csdf = _generated(oracle, lg, tuple(origin))
+        bits, csdf = world(rv, r)
+        want_bits, want_csdf = generated(oracle, lg, tuple(origin), csdf=True)
         assert np.array_equal(bits, want_bits), (lg, d)
         assert np.array_equal(csdf, want_csdf), (lg, d)
         tr, ld, cells, full = rv.scroll_region(lg, axis, d)
@@ -105,12 +52,12 @@ def test_generated_terrain(rv, oracle, sun, lg, axis):
         # a fresh context at the new seed: the same world and the same exit tables
         t = rv.StateRender(lg, 64, 64, seed=tuple(origin))
         t.world_build()
-        tb, tc = _world(rv, t)
+        tb, tc = world(rv, t)
         assert np.array_equal(bits, tb) and np.array_equal(csdf, tc), (lg, d)
-        tabs = _tables(rv, r)
-        _same_tables(tabs, _tables(rv, t), (lg, d))
+        tabs = tables(rv, r)
+        same_tables(tabs, tables(rv, t), (lg, d))
         t.close()
-        vox = _voxels(bits, lg)
+        vox = voxels(bits, lg)
         E.check_tables(E.reference(vox, sun), *tabs, f"{lg} scrolled by {d}")
         # the case itself: the slab that entered is neither all solid nor all empty, and both rebuilt
         # boxes hold a spread of distances (a wrong stride or clip cannot pass by luck)
@@ -132,17 +79,17 @@ def test_imported_sparse_worlds(rv, oracle, lg, axis):
     3) or before the entering planes (x: 20, 19, 20; z: 15, 18, 15) -- the oracle's figures for these seeds,
     printed below; no seed can give the 48 cells asked for (the cell would need a gap of 100 empty cells
     around it).  test_imported_sparse_worlds_far_reach makes that assertion, in worlds of 4 voxels."""
-    S = tuple(d // 2 for d in _dims(lg))
+    S = tuple(d // 2 for d in dims(lg))
     origin = list(R.ORIGIN)
     r = rv.StateRender(lg, 64, 64, seed=R.ORIGIN)
-    r.world_import(rv.RV_WORLD_BITS, R.sparse_bits(1 << sum(lg), 2e-5, 31 + axis))
+    r.world_import(rv.RV_WORLD_BITS, sparse_bits(lg, 2e-5, 31 + axis))
     r.csdf_build()
     for d in (8, -8, 40):
         old_bits = r.world_export(rv.RV_WORLD_BITS)
         want_bits, old_csdf, want_csdf = R.scrolled(oracle, lg, axis, d, old_bits, tuple(origin))
-        r.world_scroll(*_step(axis, d))
+        r.world_scroll(*step(axis, d))
         origin[0 if axis == 0 else 1] += d
-        bits, csdf = _world(rv, r)
+        bits, csdf = world(rv, r)
         assert np.array_equal(bits, want_bits), (lg, d)
         assert np.array_equal(csdf, want_csdf.ravel()), (lg, d)
         assert r.world_scroll_info()[1:] == (rv.scroll_region(lg, axis, d)[2], False, tuple(origin))
@@ -158,16 +105,16 @@ def test_imported_sparse_worlds_far_reach(rv, oracle, lg, axis, d):
     """The 4-voxel worlds of tests/test_world_scroll_region.py, whose seeds were picked on the oracle alone:
     the expectation differs from the shifted old CSDF >= 48 cells from the trailing face and >= 48 cells
     before the entering planes, so a rebuild of narrower slabs would leave stale bytes."""
-    S = tuple(v // 2 for v in _dims(lg))
-    old_bits = R.sparse_bits(1 << sum(lg), 1e-6, R.SPARSE_SEEDS[(lg, axis, d)])
+    S = tuple(v // 2 for v in dims(lg))
+    old_bits = sparse_bits(lg, 1e-6, R.SPARSE_SEEDS[(lg, axis, d)])
     want_bits, old_csdf, want_csdf = R.scrolled(oracle, lg, axis, d, old_bits)
     reach = R.reaches(axis, d, S, want_csdf != old_csdf)
     assert min(reach) >= 48, (lg, d, reach)
     r = rv.StateRender(lg, 64, 64, seed=R.ORIGIN)
     r.world_import(rv.RV_WORLD_BITS, old_bits)
     r.csdf_build()
-    r.world_scroll(*_step(axis, d))
-    bits, csdf = _world(rv, r)
+    r.world_scroll(*step(axis, d))
+    bits, csdf = world(rv, r)
     assert np.array_equal(bits, want_bits), (lg, d)
     assert np.array_equal(csdf, want_csdf.ravel()), (lg, d)
     assert not r.world_scroll_info()[2]
@@ -187,12 +134,12 @@ def test_both_axes_in_one_call(rv, oracle, atlas):
     cells += t.world_scroll_info()[1]
     assert cells == rv.scroll_region(lg, 0, dx)[2] + rv.scroll_region(lg, 2, dz)[2]
     assert r.world_scroll_info() == (1, cells, False, (0, 8)) and t.world_scroll_info()[0] == 2
-    bits, csdf = _world(rv, r)
-    tb, tc = _world(rv, t)
+    bits, csdf = world(rv, r)
+    tb, tc = world(rv, t)
     assert np.array_equal(bits, tb) and np.array_equal(csdf, tc)
-    assert np.array_equal(_gi(rv, r), _gi(rv, t))
-    _same_tables(_tables(rv, r), _tables(rv, t), "x then z")
-    want_bits, want_csdf = _generated(oracle, lg, (0, 8))
+    assert np.array_equal(gi(rv, r), gi(rv, t))
+    same_tables(tables(rv, r), tables(rv, t), "x then z")
+    want_bits, want_csdf = generated(oracle, lg, (0, 8), csdf=True)
     assert np.array_equal(bits, want_bits) and np.array_equal(csdf, want_csdf)
     r.close()
     t.close()
@@ -208,16 +155,16 @@ def test_fallback_and_every_voxel_entering(rv, oracle, sun):
         r.world_scroll(dx, dz)
         origin = (origin[0] + dx, origin[1] + dz)
         assert r.world_scroll_info() == (n, (1 + (dx != 0 and dz != 0)) * 64 ** 3, True, origin)
-        bits, csdf = _world(rv, r)
-        want_bits, want_csdf = _generated(oracle, lg, origin)
+        bits, csdf = world(rv, r)
+        want_bits, want_csdf = generated(oracle, lg, origin, csdf=True)
         assert np.array_equal(bits, want_bits) and np.array_equal(csdf, want_csdf), (dx, dz)
     t = rv.StateRender(lg, 64, 64, seed=origin)
     t.world_build()
-    tabs = _tables(rv, r)
-    _same_tables(tabs, _tables(rv, t), "fallback")
-    E.check_tables(E.reference(_voxels(bits, lg), sun), *tabs, "fallback")
+    tabs = tables(rv, r)
+    same_tables(tabs, tables(rv, t), "fallback")
+    E.check_tables(E.reference(voxels(bits, lg), sun), *tabs, "fallback")
     # every voxel entered with the last step: the GI grid is a fresh init's
-    assert np.array_equal(_gi(rv, r), _gi(rv, t))
+    assert np.array_equal(gi(rv, r), gi(rv, t))
     r.close()
     t.close()
 
@@ -225,37 +172,37 @@ def test_fallback_and_every_voxel_entering(rv, oracle, sun):
 # ---------------------------------------------------------------- 5. composition
 def test_composition_and_edits(rv, oracle):
     lg = (9, 6, 6)
-    X, Y, Z = _dims(lg)
+    X, Y, Z = dims(lg)
     r, t = (rv.StateRender(lg, 64, 64, seed=(64, 64)) for _ in range(2))
     for c in (r, t):
         c.world_build()
-    bits0, csdf0 = _world(rv, r)
-    tabs0 = _tables(rv, r)
+    bits0, csdf0 = world(rv, r)
+    tabs0 = tables(rv, r)
     # +8, +16 against +24
     r.world_scroll(8, 0)
     r.world_scroll(16, 0)
     t.world_scroll(24, 0)
-    bits, csdf = _world(rv, r)
-    tb, tc = _world(rv, t)
+    bits, csdf = world(rv, r)
+    tb, tc = world(rv, t)
     assert np.array_equal(bits, tb) and np.array_equal(csdf, tc)
     assert not np.array_equal(bits, bits0)
-    _same_tables(_tables(rv, r), _tables(rv, t), "+8 +16 / +24")
+    same_tables(tables(rv, r), tables(rv, t), "+8 +16 / +24")
     # ... and back: bits, CSDF and exits of the unedited world
     r.world_scroll(-24, 0)
-    bits, csdf = _world(rv, r)
+    bits, csdf = world(rv, r)
     assert np.array_equal(bits, bits0) and np.array_equal(csdf, csdf0)
-    _same_tables(_tables(rv, r), tabs0, "+24 -24")
+    same_tables(tables(rv, r), tabs0, "+24 -24")
     assert r.world_scroll_info()[3] == (64, 64)
     # an edit inside the part a scroll retains arrives shifted (and one in the part that leaves is gone)
     boxes = [(200, 36, 20, 209, 47, 29, 1), (203, 38, 22, 206, 44, 26, 0), (3, 50, 3, 6, 53, 6, 1)]
     r.world_edit(boxes)
-    edited = _voxels(r.world_export(rv.RV_WORLD_BITS), lg)
+    edited = voxels(r.world_export(rv.RV_WORLD_BITS), lg)
     assert edited[25, 40, 201] and not edited[24, 40, 204] and edited[4, 51, 4]
     r.world_scroll(40, 0)
-    bits, csdf = _world(rv, r)
-    vox = _voxels(bits, lg)
+    bits, csdf = world(rv, r)
+    vox = voxels(bits, lg)
     assert np.array_equal(vox[:, :, :X - 40], edited[:, :, 40:])
-    gen = _voxels(_generated(oracle, lg, (104, 64))[0], lg)
+    gen = voxels(generated(oracle, lg, (104, 64), csdf=True)[0], lg)
     assert np.array_equal(vox[:, :, X - 40:], gen[:, :, X - 40:])
     assert vox[25, 40, 161] and not vox[24, 40, 164]
     ow = oracle.OracleWorld(*lg)
@@ -271,17 +218,17 @@ def test_composition_and_edits(rv, oracle):
 @pytest.mark.parametrize("saturate", [False, True])
 @pytest.mark.parametrize("lg,axis,d,seed", [((9, 6, 6), 0, 16, (40, -24)), ((6, 6, 9), 2, -24, (300, -500))])
 def test_gi_grid(rv, oracle, atlas, lg, axis, d, seed, saturate):
-    G = tuple(v // 4 for v in _dims(lg))
+    G = tuple(v // 4 for v in dims(lg))
     rays = 3000
     r = rv.StateRender(lg, 64, 64, atlas=atlas, seed=seed, gi_rays_per_frame=rays, gi_init_saturate=saturate)
     r.world_build()
     r.update_gi_data()
     r.update_gi_data()
-    g0 = _gi(rv, r).reshape(G[2], G[1], G[0])
+    g0 = gi(rv, r).reshape(G[2], G[1], G[0])
     traces0, relight0 = r.stats()["gi_traces"], r.gi_relight_info()
-    r.world_scroll(*_step(axis, d))
-    origin = (seed[0] + _step(axis, d)[0], seed[1] + _step(axis, d)[1])
-    g1 = _gi(rv, r).reshape(G[2], G[1], G[0])
+    r.world_scroll(*step(axis, d))
+    origin = (seed[0] + step(axis, d)[0], seed[1] + step(axis, d)[1])
+    g1 = gi(rv, r).reshape(G[2], G[1], G[0])
     # retained cells: the old grid at the new index
     g = d // 4
     ax = 2 - axis
@@ -305,35 +252,11 @@ def test_gi_grid(rv, oracle, atlas, lg, axis, d, seed, saturate):
     ow.gi[:] = g1.ravel().view(np.uint8)
     ow.gi_update(2, first=2 * rays, count=rays)
     r.update_gi_data()
-    assert np.array_equal(_gi(rv, r), ow.gi.view(np.uint32))
+    assert np.array_equal(gi(rv, r), ow.gi.view(np.uint32))
     r.close()
 
 
 # ---------------------------------------------------------------- 7. frames across a scroll
-def _draw(r, d):
-    c = d.cam
-    r.draw_cuda(c.pos[:], c.forward[:], c.up[:], c.right[:], np.ctypeslib.as_array(d.vp),
-                np.ctypeslib.as_array(d.prev_vp), 0.0, d.time)
-
-
-def _same_frames(rv, r, t, what):
-    for k in (rv.RV_IMAGE_COLOR, rv.RV_IMAGE_MOTION, rv.RV_IMAGE_DEPTH):
-        assert np.array_equal(r.readback(k), t.readback(k)), (what, k)
-    assert np.array_equal(_gi(rv, r), _gi(rv, t)), what
-
-
-def _shifted(rv, d, dx, dz):
-    cam, vp, pvp = rv.scroll_view(dx, dz, d.cam, np.ctypeslib.as_array(d.vp), np.ctypeslib.as_array(d.prev_vp))
-    return rv.frame_desc(cam, vp, pvp, d.time, d.jitter_x, d.jitter_y)
-
-
-def _ctx128(rv, atlas, **kw):
-    c = rv.StateRender((7, 7, 7), W, H, flags=rv.RV_FLAGS_REFERENCE, atlas=atlas, gi_rays_per_frame=4096, **kw)
-    c.world_build()
-    c.gi_update(0)
-    return c
-
-
 def _modes(mode, in_flight, ahead, plain):
     """ahead: the defaults of the mode (work computed ahead); plain: nothing computed ahead."""
     if mode == "draw":
@@ -355,7 +278,7 @@ def _run(rv, ctxs, mode, descs, nxt, flags):
         if mode == "draw":
             for d in descs:
                 c.update_gi_data()
-                _draw(c, d)
+                draw(c, d)
         else:
             c.render_frame_seq(descs, next_desc=nxt, flags=flags, gi_per_frame=True)
 
@@ -371,23 +294,23 @@ def test_frames_across_a_scroll(rv, oracle, atlas, mode, in_flight):
     flags = rv.RV_FLAGS_REFERENCE
     n = 4 if mode == "group" else 3
     seq = camera_path(TEST_POSES_128["P0"], W, H, 2 * n, pan=0.01, ref_compat=True)
-    r, t = _ctx128(rv, atlas), _ctx128(rv, atlas)
+    r, t = ctx128(rv, atlas, W, H, 4096), ctx128(rv, atlas, W, H, 4096)
     if mode == "two":
         r.set_flow(0)
     _modes("draw" if mode == "two" else mode, in_flight, [r], t)
     m = "draw" if mode == "two" else mode
     _run(rv, (r, t), m, seq[:n], seq[n], flags)
-    _same_frames(rv, r, t, "before")
+    same_frames(rv, r, t, "before")
     r.world_scroll(dx, dz)
-    want_bits, want_csdf = _generated(oracle, lg, (dx, dz))
-    bits, csdf = _world(rv, r)
+    want_bits, want_csdf = generated(oracle, lg, (dx, dz), csdf=True)
+    bits, csdf = world(rv, r)
     assert np.array_equal(bits, want_bits) and np.array_equal(csdf, want_csdf)
     t.world_import(rv.RV_WORLD_BITS, want_bits)
     t.world_import(rv.RV_WORLD_CSDF, want_csdf)
     t.world_import(rv.RV_WORLD_GI, r.world_export(rv.RV_WORLD_GI))
-    after = [_shifted(rv, d, dx, dz) for d in seq[n:]]
+    after = [shifted(rv, d, dx, dz) for d in seq[n:]]
     _run(rv, (r, t), m, after[:n], after[n], flags)
-    _same_frames(rv, r, t, "after")
+    same_frames(rv, r, t, "after")
     assert r.flow_info()[2] == 0
     if mode == "draw" and in_flight == 1:
         assert r.flow_info()[0] and r.flow_info()[1] == 2 * n and not t.flow_info()[0]
@@ -397,7 +320,7 @@ def test_frames_across_a_scroll(rv, oracle, atlas, mode, in_flight):
         c.stats_reset()
         c.frame(d.cam, np.ctypeslib.as_array(d.vp), np.ctypeslib.as_array(d.prev_vp), time=d.time,
                 jx=d.jitter_x, jy=d.jitter_y, flags=flags | rv.RV_F_STATS)
-    _same_frames(rv, r, t, "stats frame")
+    same_frames(rv, r, t, "stats frame")
     for stage in (0, 2):   # pre-pass and render: the blocks a flow frame and a two-launch frame both fill
         assert r.stats(stage) == t.stats(stage), stage
     assert r.stats(2)["primary"] == W * H
@@ -411,13 +334,13 @@ def test_null_scroll_keeps_the_work_computed_ahead(rv, atlas, mode):
     flags = rv.RV_FLAGS_REFERENCE
     n = 3
     seq = camera_path(TEST_POSES_128["P0"], W, H, 2 * n, pan=0.01, ref_compat=True)
-    a, b = _ctx128(rv, atlas), _ctx128(rv, atlas)
+    a, b = ctx128(rv, atlas, W, H, 4096), ctx128(rv, atlas, W, H, 4096)
     _run(rv, (a, b), mode, seq[:n], seq[n], flags)
     info = a.world_scroll_info()
     a.world_scroll(0, 0)
     assert a.world_scroll_info() == info == (0, 0, False, (0, 0))
     _run(rv, (a, b), mode, seq[n:2 * n], seq[2 * n], flags)
-    _same_frames(rv, a, b, "after the null scroll")
+    same_frames(rv, a, b, "after the null scroll")
     # a discarded update or pre-pass would have been traced a second time
     assert a.stats() == b.stats()
     assert a.flow_info() == b.flow_info()
@@ -432,8 +355,8 @@ def test_status_origin_and_seed(rv, oracle):
     with pytest.raises(rv.RvError, match="RV_ERR_STATE"):
         r.world_scroll(8, 0)
     r.world_build()
-    bits, csdf = _world(rv, r)
-    gi = _gi(rv, r)
+    bits, csdf = world(rv, r)
+    gi0 = gi(rv, r)
     for bad in ((4, 0), (0, -12), (7, 8), (8, 1)):
         with pytest.raises(rv.RvError, match="RV_ERR_INVALID"):
             r.world_scroll(*bad)
@@ -443,16 +366,16 @@ def test_status_origin_and_seed(rv, oracle):
             r.world_scroll(*bad)
     r.world_scroll(0, 0)
     assert r.world_scroll_info() == (0, 0, False, (-24, -8))
-    nb, nc = _world(rv, r)
-    assert np.array_equal(nb, bits) and np.array_equal(nc, csdf) and np.array_equal(_gi(rv, r), gi)
+    nb, nc = world(rv, r)
+    assert np.array_equal(nb, bits) and np.array_equal(nc, csdf) and np.array_equal(gi(rv, r), gi0)
     # a later world_build regenerates the scrolled window
     r.world_scroll(-16, 40)
     assert r.world_scroll_info() == (1, 2 * 64 * 32 * 64, True, (-40, 32))
-    nb, nc = _world(rv, r)
+    nb, nc = world(rv, r)
     r.world_build()
-    bb, bc = _world(rv, r)
+    bb, bc = world(rv, r)
     assert np.array_equal(bb, nb) and np.array_equal(bc, nc) and not np.array_equal(nb, bits)
-    want_bits, want_csdf = _generated(oracle, lg, (-40, 32))
+    want_bits, want_csdf = generated(oracle, lg, (-40, 32), csdf=True)
     assert np.array_equal(bb, want_bits) and np.array_equal(bc, want_csdf)
     assert r.world_scroll_info()[3] == (-40, 32)
     # the largest origins are reachable
@@ -464,25 +387,6 @@ def test_status_origin_and_seed(rv, oracle):
 
 
 # ---------------------------------------------------------------- 9. two-rank loopback
-def _run_ranks(fns):
-    errs = [None] * len(fns)
-
-    def body(q):
-        try:
-            fns[q]()
-        except BaseException as e:   # noqa: BLE001 -- re-raised below
-            errs[q] = e
-    ts = [threading.Thread(target=body, args=(q,)) for q in range(len(fns))]
-    for th in ts:
-        th.start()
-    for th in ts:
-        th.join(timeout=300)
-        assert not th.is_alive(), "a rank thread hung"
-    for e in errs:
-        if e is not None:
-            raise e
-
-
 def test_two_rank_loop_with_a_scroll_equals_one_rank(rv, atlas):
     """Both ranks of a tile-sharded loop scroll between two calls: the gathered frame and every rank's GI
     grid equal one context rendering whole frames one at a time with the same scroll."""
@@ -490,11 +394,11 @@ def test_two_rank_loop_with_a_scroll_equals_one_rank(rv, atlas):
     N, (dx, dz) = 2, (-8, 16)
     flags = rv.RV_FLAGS_REFERENCE
     seq = camera_path(TEST_POSES_128["P0"], W, H, 8, pan=0.02, ref_compat=True)
-    seq = seq[:4] + [_shifted(rv, d, dx, dz) for d in seq[4:]]
-    ref = _ctx128(rv, atlas)
+    seq = seq[:4] + [shifted(rv, d, dx, dz) for d in seq[4:]]
+    ref = ctx128(rv, atlas, W, H, 4096)
     ref.set_pipeline(0)
     group = rv.LoopbackGroup(N, timeout_ms=60000)
-    rs = [_ctx128(rv, atlas) for _ in range(N)]
+    rs = [ctx128(rv, atlas, W, H, 4096) for _ in range(N)]
     comms = []
     for q, c in enumerate(rs):
         c.set_tile_shard(32, q, N)
@@ -503,8 +407,8 @@ def test_two_rank_loop_with_a_scroll_equals_one_rank(rv, atlas):
         if a:
             for c in rs + [ref]:
                 c.world_scroll(dx, dz)
-        _run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b], flags=flags, gi_per_frame=True,
-                                                       comm=comms[q]) for q in range(N)])
+        run_ranks([lambda q=q: rs[q].render_frame_seq(seq[a:b], next_desc=seq[b], flags=flags, gi_per_frame=True,
+                                                      comm=comms[q]) for q in range(N)])
         for m in comms:
             m.wait(60000)
         for k in range(a, b):

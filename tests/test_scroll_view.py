@@ -8,14 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 CASES = [(8, 0), (0, -8), (64, -16), (-4096, 2048), (3, -5), (0, 0), (1 << 20, -(1 << 20))]
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def views(rv):

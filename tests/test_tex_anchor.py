@@ -7,17 +7,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_world import rv
 import np_shade as S
 import np_tex_anchor as A
 
 ORIGINS = [(0, 0), (8, 0), (40, -16), (123464, -98760), (2 ** 24 + 8, -2 ** 24 - 16)]
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 @pytest.fixture(scope="module")

@@ -6,15 +6,10 @@ than the edit's coarse extent grown by 64 cells per axis."""
 import numpy as np
 import pytest
 
+from gpu_world import rv
+
 WORLDS = [(10, 6, 6), (6, 10, 6), (6, 6, 10)]
 DENSITIES = [0.0, 1e-6, 1e-4]
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def sparse_world(oracle, lg, density, seed):

@@ -7,14 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_world import rv
+from np_world import column_bits
+
 WORLDS = [(7, 6, 7), (9, 7, 7), (7, 7, 9), (6, 8, 6)]   # lbx != lbz both ways; ly below and above lx
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
 
 
 def brick_array(vox):
@@ -24,11 +20,6 @@ def brick_array(vox):
     v = vox.reshape(Z // 8, 8, Y // 8, 8, X // 8, 8)       # bz, z, by, y, bx, x
     v = v.transpose(4, 2, 0, 1, 3, 5)                       # bx, by, bz | z, y, x: bz fastest of the bricks
     return np.packbits(v.reshape(-1), bitorder="little").view(np.uint32)
-
-
-def column_bits(vox, bx, bz):
-    """Column bits of brick column (bx, bz): RV_WORLD_BITS' layout for log2 dims (3, ly, 3)."""
-    return np.packbits(vox[8 * bz:8 * bz + 8, :, 8 * bx:8 * bx + 8].reshape(-1), bitorder="little").view(np.uint32)
 
 
 def columns_of(lg):

@@ -10,39 +10,10 @@ region would fail."""
 import numpy as np
 import pytest
 
+from gpu_world import rv, sparse_bits
+from np_world import SPARSE_SEEDS, expected_plan, reaches, scrolled
+
 WORLDS = [(9, 7, 7), (7, 7, 9), (10, 6, 6), (7, 7, 7)]
-
-
-@pytest.fixture(scope="module")
-def rv():
-    import rvgrt_amd
-    rvgrt_amd._lib.load()
-    return rvgrt_amd
-
-
-def expected_plan(lg, axis, d):
-    """(trailing, leading, cells, full) restated: k = |d| / 2 cells; the final byte can change within 64
-    cells of the face the old planes left through and of the entering planes."""
-    S = [1 << (l - 1) for l in lg]
-    Sa, k = S[axis], abs(d) // 2
-    whole = (0, S[0], 0, S[1], 0, S[2])
-    if d == 0:
-        return (0,) * 6, (0,) * 6, 0, False
-    if d > 0:
-        tr, ld = (0, min(Sa, 64)), (max(0, Sa - k - 64), Sa)
-        touch = ld[0] <= tr[1]
-    else:
-        tr, ld = (max(0, Sa - 64), Sa), (0, min(Sa, k + 64))
-        touch = tr[0] <= ld[1]
-    if abs(d) >= 2 * Sa or touch or 640 + 4 * k >= 4 * Sa:
-        return whole, (0,) * 6, S[0] * S[1] * S[2], True
-    boxes = []
-    for r in (tr, ld):
-        b = list(whole)
-        b[2 * axis], b[2 * axis + 1] = r
-        boxes.append(tuple(b))
-    cross = S[0] * S[1] * S[2] // Sa
-    return boxes[0], boxes[1], ((tr[1] - tr[0]) + (ld[1] - ld[0])) * cross, False
 
 
 @pytest.mark.parametrize("lg", WORLDS)
@@ -95,77 +66,13 @@ def test_invalid_arguments(rv):
 
 
 # ---------------------------------------------------------------- the bound, against the oracle
-ORIGIN = (40, -24)   # the old window's origin on the terrain
-# Seeds of the density-1e-6 worlds (4 solid voxels) in which the oracle alone shows a byte that differs
-# >= 48 cells from the trailing face: one of the voxels leaves with the old planes and was the nearest
-# solid of cells that far into the retained part.  (The entering terrain reaches as far by itself.)
-SPARSE_SEEDS = {
-    ((10, 6, 6), 0, 8): 1119, ((10, 6, 6), 0, -8): 1036, ((10, 6, 6), 0, 64): 1005, ((10, 6, 6), 0, -64): 1049,
-    ((6, 6, 10), 2, 8): 1036, ((6, 6, 10), 2, -8): 1074, ((6, 6, 10), 2, 64): 1009, ((6, 6, 10), 2, -64): 1037,
-    ((10, 6, 6), 0, 40): 1060, ((6, 6, 10), 2, 40): 1027,
-}
-
-
-def sparse_bits(n, density, seed):
-    bits = np.zeros(n // 32, np.uint32)
-    idx = np.random.default_rng(seed).choice(n, int(round(n * density)), replace=False)
-    np.bitwise_or.at(bits, idx >> 5, (np.uint32(1) << (idx & 31).astype(np.uint32)))
-    return bits
-
-
-_TERRAIN = {}
-
-
-def terrain(oracle, lg, ox, oz):
-    """Voxels [z, y, x] of the generated window at origin (ox, oz)."""
-    key = (lg, ox, oz)
-    if key not in _TERRAIN:
-        _TERRAIN[key] = oracle.OracleWorld(*lg, ox=ox, oz=oz).fill().voxels()
-    return _TERRAIN[key]
-
-
-def scrolled(oracle, lg, axis, d, old_bits, origin=ORIGIN):
-    """(expected bits, old CSDF moved to the new indices with 255 where a cell entered, expected CSDF) of a
-    window at `origin` holding old_bits, moved by d voxels along axis."""
-    ow = oracle.OracleWorld(*lg)
-    ow.bits[:] = old_bits
-    ow.build_csdf()
-    S = tuple(1 << (l - 1) for l in lg)
-    ax = 2 - axis   # numpy axis of [z, y, x]
-    vox = np.roll(ow.voxels(), -d, axis=ax)
-    old = np.roll(ow.csdf.reshape(S[2], S[1], S[0]), -d // 2, axis=ax)
-    new_org = (origin[0] + (d if axis == 0 else 0), origin[1] + (d if axis == 2 else 0))
-    gen = terrain(oracle, lg, *new_org)
-    n = vox.shape[ax]
-    ent = [slice(None)] * 3
-    ent[ax] = slice(n - d, n) if d > 0 else slice(0, -d)
-    vox[tuple(ent)] = gen[tuple(ent)]
-    ent[ax] = slice(n // 2 - d // 2, n // 2) if d > 0 else slice(0, -d // 2)
-    old[tuple(ent)] = 255
-    nw = oracle.OracleWorld(*lg)
-    nw.bits[:] = np.packbits(vox.ravel(), bitorder="little").view(np.uint32)
-    nw.build_csdf()
-    return nw.bits, old, nw.csdf.reshape(S[2], S[1], S[0])
-
-
-def reaches(axis, d, S, diff):
-    """How far the differing cells reach from the trailing face and before the entering planes (cells)."""
-    c = np.nonzero(diff)[2 - axis]
-    Sa, k = S[axis], abs(d) // 2
-    if d > 0:
-        tr, ld = c[c < Sa // 2], c[c >= Sa // 2]
-        return (int(tr.max()) if len(tr) else -1), (Sa - k - 1 - int(ld.min()) if len(ld) else -1)
-    tr, ld = c[c >= Sa // 2], c[c < Sa // 2]
-    return (Sa - 1 - int(tr.min()) if len(tr) else -1), (int(ld.max()) - k if len(ld) else -1)
-
-
 @pytest.mark.parametrize("density", [0.0, 1e-6, 1e-4])
 @pytest.mark.parametrize("d", [8, -8, 40, 64, -64])
 @pytest.mark.parametrize("lg,axis", [((10, 6, 6), 0), ((6, 6, 10), 2)])
 def test_slabs_hold_every_changed_cell(rv, oracle, lg, axis, d, density):
     S = tuple(1 << (l - 1) for l in lg)
     seed = SPARSE_SEEDS[(lg, axis, d)] if density == 1e-6 else 99 + axis + abs(d)
-    bits, old, new = scrolled(oracle, lg, axis, d, sparse_bits(1 << sum(lg), density, seed))
+    bits, old, new = scrolled(oracle, lg, axis, d, sparse_bits(lg, density, seed))
     tr, ld, cells, full = rv.scroll_region(lg, axis, d)
     assert not full
     inside = np.zeros(new.shape, bool)
