@@ -77,6 +77,21 @@ class rv_gi_box(C.Structure):
 RV_RELIGHT_INIT = 1
 RV_RELIGHT_MAX_RECORDS = 1 << 23
 
+
+class rv_body(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("size", C.c_float * 3), ("delta", C.c_float * 3)]
+
+
+class rv_body_out(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+# rv_body_out.flags, rv_world_bodies_move's flags
+RV_BODY_XN, RV_BODY_XP, RV_BODY_YN, RV_BODY_YP, RV_BODY_ZN, RV_BODY_ZP = 1, 2, 4, 8, 16, 32
+RV_BODY_START_SOLID, RV_BODY_EDGE, RV_BODY_INVALID = 64, 128, 256
+RV_BODIES_OPEN_EDGES = 1
+RV_BODIES_MAX = 1 << 24
+
 STAT_FIELDS = ["traces", "primary", "shadow", "refl", "refl_shadow", "prepass_primary",
                "prepass_shadow", "cones", "cone_steps", "sphere_steps", "dda_steps",
                "csdf_checks", "tex_samples", "undef_hits", "gi_traces", "frames"]
@@ -141,6 +156,10 @@ SIGNATURES = [
     ("rv_world_store_clear", I32, [P]),
     ("rv_world_columns_read", I32, [P, P, I32, P, SZ]),
     ("rv_persist_column_map", I32, [I32, I32, I32, I32, I32, P]),
+    ("rv_world_bodies_move", I32, [P, P, I64, I32, P]),
+    ("rv_world_bodies_move_device", I32, [P, P, I64, I32, P]),
+    ("rv_world_bodies_move_at", I32, [I32, I32, I32, P, P, I64, I32, P]),
+    ("rv_world_bodies_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("rv_texture_origin_set", I32, [P, I32, I32]),
     ("rv_texture_follow_scroll", I32, [P, I32]),
     ("rv_texture_origin_get", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

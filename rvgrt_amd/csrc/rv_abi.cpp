@@ -167,6 +167,7 @@ void rv_destroy(rv_ctx* c) {
     hipFree(c->scroll_tmp);
     hipFree(c->persist_cols); hipFree(c->persist_stage);
     if (c->persist_stage_h) hipHostFree(c->persist_stage_h);
+    hipFree(c->bodies_in); hipFree(c->bodies_out);
     hipFree(c->tiles.d); hipFree(c->untile_ids.d);
     hipFree(c->tilebuf);
     hipFree(c->hpos); hipFree(c->hinfo); hipFree(c->hsec); hipFree(c->pphit); hipFree(c->qcount);

@@ -7,7 +7,8 @@
 //   rv_edit.cpp   voxel edits in place (rv_world_edit);
 //   rv_relight.cpp  the GI refresh of a cell box (rv_gi_relight);
 //   rv_scroll.cpp   the world window moved over the terrain (rv_world_scroll);
-//   rv_persist.cpp  edited columns kept across scrolls (rv_world_persist).
+//   rv_persist.cpp  edited columns kept across scrolls (rv_world_persist);
+//   rv_bodies.cpp   swept box collision against the voxel window (rv_world_bodies_move).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -257,6 +258,10 @@ struct rv_ctx {
     std::vector<int2> persist_cols_h;
     uint32_t* persist_stage_h = nullptr; size_t persist_stage_h_cap = 0;   // pinned: the two 1-MiB copies of a C4 step
     uint64_t persist_captured = 0, persist_restored = 0;
+    // rv_world_bodies_move (rv_bodies.cpp): the host form's device copies of its arrays (kept between calls;
+    // caps in bytes) and rv_world_bodies_info's sums
+    void* bodies_in = nullptr; void* bodies_out = nullptr; size_t bodies_in_cap = 0, bodies_out_cap = 0;
+    uint64_t bodies_calls = 0, bodies_moved = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;

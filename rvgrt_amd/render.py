@@ -150,6 +150,37 @@ def texture_tile_at(ox, oz, pos):
     return out
 
 
+def _bodies(lo, size, delta):
+    """(n, 9) float32 rows lo | size | delta: an array of rv_body.  size and delta broadcast."""
+    lo = np.asarray(lo, np.float32).reshape(-1, 3)
+    b = np.empty((len(lo), 9), np.float32)
+    b[:, 0:3] = lo
+    b[:, 3:6] = np.asarray(size, np.float32)
+    b[:, 6:9] = np.asarray(delta, np.float32)
+    return b
+
+
+def _bodies_out(out):
+    """An array of rv_body_out as (lo (n, 3) float32, flags (n,) uint32)."""
+    return np.ascontiguousarray(out[:, :3]).view(np.float32), out[:, 3].copy()
+
+
+def bodies_move_at(log2_dims, bits, lo, size, delta, flags=0):
+    """rv_world_bodies_move_at (host only): the swept box collision the kernel evaluates,
+    on the CPU over `bits` (RV_WORLD_BITS layout, log2_x >= 5).  Returns (lo, flags)."""
+    L = _lib.load()
+    bits = np.ascontiguousarray(bits, np.uint32)
+    if bits.size != (1 << sum(int(v) for v in log2_dims)) // 32:
+        raise ValueError("bits does not match log2_dims")
+    b = _bodies(lo, size, delta)
+    out = np.zeros((len(b), 4), np.uint32)
+    st = L.rv_world_bodies_move_at(int(log2_dims[0]), int(log2_dims[1]), int(log2_dims[2]), _ptr(bits), _ptr(b),
+                                   len(b), int(flags), _ptr(out))
+    if st != 0:
+        raise RvError(f"rv_world_bodies_move_at: {_lib.STATUS_NAMES.get(st, st)}")
+    return _bodies_out(out)
+
+
 def rccl_path():
     """The RCCL of the HIP runtime this process uses: torch's bundled librccl
     when torch is already imported (the library then shares torch's runtime),
@@ -501,6 +532,29 @@ class StateRender:
         out = np.zeros(len(p), np.uint8)
         self._check(self._L.rv_texture_tiles(self._h, _ptr(p), len(p), _ptr(out)), "rv_texture_tiles")
         return out
+
+    def bodies_move(self, lo, size, delta, flags=0):
+        """rv_world_bodies_move: n boxes [lo, lo + size) in grid coordinates moved by delta
+        through the voxel bits with per-axis collision (y, x, z).  lo is (n, 3); size and
+        delta broadcast against it.  Returns (lo (n, 3) float32, flags (n,) uint32 of
+        RV_BODY_*).  Synchronous."""
+        b = _bodies(lo, size, delta)
+        out = np.zeros((len(b), 4), np.uint32)
+        self._check(self._L.rv_world_bodies_move(self._h, _ptr(b), len(b), int(flags), _ptr(out)),
+                    "rv_world_bodies_move")
+        return _bodies_out(out)
+
+    def bodies_move_device(self, dev_in: int, n: int, dev_out: int, flags=0):
+        """rv_world_bodies_move_device: n rv_body at device address dev_in -> n rv_body_out
+        at dev_out, enqueued on the context's stream (not synchronous)."""
+        self._check(self._L.rv_world_bodies_move_device(self._h, C.c_void_p(dev_in), int(n), int(flags),
+                                                        C.c_void_p(dev_out)), "rv_world_bodies_move_device")
+
+    def bodies_info(self):
+        """(calls, bodies): sums over the bodies_move calls that did work."""
+        n, b = C.c_uint64(), C.c_uint64()
+        self._check(self._L.rv_world_bodies_info(self._h, C.byref(n), C.byref(b)), "rv_world_bodies_info")
+        return int(n.value), int(b.value)
 
     def gi_relight(self, box, frame0, iterations, init=False):
         """rv_gi_relight: `iterations` update steps (RNG frames frame0, frame0 + 1, ...)
