@@ -44,21 +44,19 @@ rv_status rv_create(const rv_config* cfg, int32_t device, rv_ctx** out) {
     c->brick_bytes = dtop_byte(w.coff, w.X, w.Z) + dtop_bytes(w.X, w.Z);
     c->gi_bytes = n_gi(c) * 4;
 
-    auto cleanup_fail = [&](rv_status s, const char* what) {
-        std::string m = std::string("rv_create: ") + what;
+    auto cleanup_fail = [&](rv_status s) {   // whatever was built so far goes with the context
         rv_destroy(c);
-        (void)m;
         return s;
     };
-    if (hipMalloc(&c->brick, c->brick_bytes) != hipSuccess) return cleanup_fail(RV_ERR_OOM, "bricks");
-    if (hipMalloc(&c->gi, c->gi_bytes) != hipSuccess) return cleanup_fail(RV_ERR_OOM, "gi");
-    hipMemset(c->brick, 0, horizon_byte(w.coff));
-    hipMemset(reinterpret_cast<char*>(c->brick) + horizon_byte(w.coff), 0xFF, horizon_bytes(w.X, w.Z));   // no sun exit
-    hipMemset(reinterpret_cast<char*>(c->brick) + dtop_byte(w.coff, w.X, w.Z), 0x7F, dtop_bytes(w.X, w.Z));   // no skip
+    if (c->brick.reserve(c, c->brick_bytes) || c->gi.reserve(c, c->gi_bytes)) return cleanup_fail(RV_ERR_OOM);
+    char* const brick = reinterpret_cast<char*>(c->brick.p);
+    hipMemset(brick, 0, horizon_byte(w.coff));
+    hipMemset(brick + horizon_byte(w.coff), 0xFF, horizon_bytes(w.X, w.Z));   // no sun exit
+    hipMemset(brick + dtop_byte(w.coff, w.X, w.Z), 0x7F, dtop_bytes(w.X, w.Z));   // no skip
     hipMemset(c->gi, 0, c->gi_bytes);
     // atlas
     int aw = cfg->atlas_rgba8 ? cfg->atlas_w : 256, ah = cfg->atlas_rgba8 ? cfg->atlas_h : 256;
-    if (aw <= 0 || ah <= 0) return cleanup_fail(RV_ERR_INVALID, "atlas dims");
+    if (aw <= 0 || ah <= 0) return cleanup_fail(RV_ERR_INVALID);
     w.aw = aw; w.ah = ah;
     // held in World's tiled layout (rv_device.h atlas_tiled_off): 128-B lines of 2D texel blocks
     std::vector<uint32_t> tiled(atlas_tiled_texels(aw, ah), 0u);
@@ -68,7 +66,7 @@ rv_status rv_create(const rv_config* cfg, int32_t device, rv_ctx** out) {
             if (cfg->atlas_rgba8) std::memcpy(&t, static_cast<const uint8_t*>(cfg->atlas_rgba8) + 4 * ((size_t)r * aw + q), 4);
             tiled[atlas_tiled_off(aw, r, q)] = t;
         }
-    if (hipMalloc(&c->atlas, tiled.size() * 4) != hipSuccess) return cleanup_fail(RV_ERR_OOM, "atlas");
+    if (c->atlas.reserve(c, tiled.size() * 4)) return cleanup_fail(RV_ERR_OOM);
     hipMemcpy(c->atlas, tiled.data(), tiled.size() * 4, hipMemcpyHostToDevice);
     c->cfg.atlas_rgba8 = nullptr;
     // frame slot 0 (more with rv_set_frames_in_flight)
@@ -78,32 +76,27 @@ rv_status rv_create(const rv_config* cfg, int32_t device, rv_ctx** out) {
     c->own_depth_pitch = align256((size_t)W * 2);
     c->color_pitch = c->own_color_pitch; c->mv_pitch = c->own_mv_pitch; c->depth_pitch = c->own_depth_pitch;
     c->slots.resize(1);
-    if (!slot_alloc(c, c->slots[0])) return cleanup_fail(RV_ERR_OOM, "frame slot");
+    if (!slot_alloc(c, c->slots[0])) return cleanup_fail(RV_ERR_OOM);
     slot_load(c, 0);
-    if (hipMalloc(&c->counters, NSTAGE * NCNT * sizeof(unsigned long long)) != hipSuccess)
-        return cleanup_fail(RV_ERR_OOM, "counters");
+    if (c->counters.reserve(c, NSTAGE * NCNT * sizeof(unsigned long long))) return cleanup_fail(RV_ERR_OOM);
     hipMemset(c->counters, 0, NSTAGE * NCNT * sizeof(unsigned long long));
     {   // wavefront stage buffers
         size_t npx = (size_t)W * H, nhalf = (size_t)(W / 2) * (H / 2);
-        bool ok = hipMalloc(&c->hpos, npx * 16) == hipSuccess && hipMalloc(&c->hinfo, npx * 4) == hipSuccess &&
-                  hipMalloc(&c->hsec, npx * 16) == hipSuccess && hipMalloc(&c->pphit, nhalf * 16) == hipSuccess &&
-                  hipMalloc(&c->qcount, QCOUNT_BYTES) == hipSuccess;
-        if (!ok) return cleanup_fail(RV_ERR_OOM, "wavefront buffers");
+        if (c->hpos.reserve(c, npx * 16) || c->hinfo.reserve(c, npx * 4) || c->hsec.reserve(c, npx * 16) ||
+            c->pphit.reserve(c, nhalf * 16) || c->qcount.reserve(c, QCOUNT_BYTES))
+            return cleanup_fail(RV_ERR_OOM);
         hipMemset(c->qcount, 0, QCOUNT_BYTES);   // queues themselves: sized per frame by ensure_queues
     }
 #ifdef RV_WAVE_TRACE
-    if (getenv("RV_WAVE_TRACE")) {
-        c->wtrace_bytes = (size_t)sched_grid<8, 8>(SCHED_COST, W, H) * 32;   // one 32-B record per 8x8-pixel wave tile
-        if (hipMalloc(&c->wtrace, c->wtrace_bytes) != hipSuccess) return cleanup_fail(RV_ERR_OOM, "wave trace");
-        hipMemset(c->wtrace, 0, c->wtrace_bytes);
+    if (getenv("RV_WAVE_TRACE")) {   // one 32-B record per 8x8-pixel wave tile
+        if (c->wtrace.reserve(c, (size_t)sched_grid<8, 8>(SCHED_COST, W, H) * 32)) return cleanup_fail(RV_ERR_OOM);
+        hipMemset(c->wtrace, 0, c->wtrace.cap);
     }
 #endif
-    if (hipEventCreateWithFlags(&c->ev_world, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_gi_done, hipEventDisableTiming) != hipSuccess ||
-        hipDeviceGetStreamPriorityRange(&c->prio_lo, &c->prio_hi) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->gi_stream, hipStreamNonBlocking, gi_prio(c)) != hipSuccess)
-        return cleanup_fail(RV_ERR_HIP, "gi stream/events");
-    if (hipDeviceSynchronize() != hipSuccess) return cleanup_fail(RV_ERR_HIP, "init sync");
+    if (c->ev_world.ensure(c) || c->ev_gi_done.ensure(c) ||
+        hipDeviceGetStreamPriorityRange(&c->prio_lo, &c->prio_hi) != hipSuccess || c->gi_stream.ensure(c, gi_prio(c)))
+        return cleanup_fail(RV_ERR_HIP);
+    if (hipDeviceSynchronize() != hipSuccess) return cleanup_fail(RV_ERR_HIP);
     if (const char* e = getenv("RV_PIPE_MIX")) {   // A/B runs: RV_OPT_PIPE_MIX's packed value (any base)
         const long long v = strtoll(e, nullptr, 0);
         if (v >= 0 && (v >> 24) <= 0xFFFFFF) { c->pipe_mix = (uint64_t)v; c->pipe_mix_set = true; }
@@ -121,17 +114,11 @@ void rv_destroy(rv_ctx* c) {
     } else {
         hipDeviceSynchronize();   // every frame slot's stream
     }
-    hipFree(c->brick); hipFree(c->gi); hipFree(c->gi_tmp); hipFree(c->atlas); hipFree(c->tex);
-    for (auto& ph : c->pipe_half) { hipFree(ph[0]); hipFree(ph[1]); }
-    for (int q = 0; q < 2; q++) { hipFree(c->pipe_tbuf[q]); hipFree(c->pipe_gbuf[q]); }
-    hipFree(c->pipe_gi_stage); hipFree(c->pipe_gi_all);
-    for (hipEvent_t e : c->pipe_ev) if (e) hipEventDestroy(e);
     if (c->flow_wtrace) {   // RV_FLOW_WAVE_TRACE: header {len0, len1, len2, n}, then 4 dwords per workgroup
         std::vector<uint32_t> h((size_t)c->flow_wtrace_n * 4 + 4);
         h[0] = c->flow_wlen[0]; h[1] = c->flow_wlen[1]; h[2] = c->flow_wlen[2]; h[3] = c->flow_wtrace_n;
         if (hipMemcpy(h.data() + 4, c->flow_wtrace, (size_t)c->flow_wtrace_n * 16, hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE* fp = fopen(getenv("RV_FLOW_WAVE_TRACE"), "wb")) { fwrite(h.data(), 4, h.size(), fp); fclose(fp); }
-        hipFree(c->flow_wtrace);
     }
     if (c->pipe_wstat) {   // RV_PIPE_WAVE_STATS: per part, the longest wave and the 99th percentile per launch
         const char* names[3] = {"gi", "prepass", "render"};
@@ -155,55 +142,15 @@ void rv_destroy(rv_ctx* c) {
         for (int q = 0; used && q < 3; q++)
             fprintf(stderr, "[rvgrt] pipe waves %-8s longest %7.1f us  p99 %7.1f us  (mean over %u launches)\n",
                     names[q], mx[q] / used / 100.0, p99[q] / used / 100.0, used);
-        hipFree(c->pipe_wstat);
     }
-    if (!c->slots.empty()) slot_save(c);
-    for (FrameSlot& sl : c->slots) slot_free(sl);
-    hipFree(c->counters);
-    hipFree(c->d_top);
-    hipFree(c->coltop);
-    hipFree(c->edit_boxes); hipFree(c->edit_flag); hipFree(c->edit_t0); hipFree(c->edit_t1);
-    hipFree(c->relight_rec); hipFree(c->relight_dense[0]); hipFree(c->relight_dense[1]);
-    hipFree(c->scroll_tmp);
-    hipFree(c->persist_cols); hipFree(c->persist_stage);
-    if (c->persist_stage_h) hipHostFree(c->persist_stage_h);
-    hipFree(c->bodies_in); hipFree(c->bodies_out);
-    hipFree(c->tiles.d); hipFree(c->untile_ids.d);
-    hipFree(c->tilebuf);
-    hipFree(c->hpos); hipFree(c->hinfo); hipFree(c->hsec); hipFree(c->pphit); hipFree(c->qcount);
-    for (int q = 0; q < NQUEUE; q++) hipFree(c->wq[q]);
-    for (hipEvent_t e : c->ev) hipEventDestroy(e);
 #ifdef RV_WAVE_TRACE
     if (c->wtrace) {   // env RV_WAVE_TRACE=<file>: dump the last frame's wave records
-        std::vector<uint32_t> h(c->wtrace_bytes / 4);
-        if (hipMemcpy(h.data(), c->wtrace, c->wtrace_bytes, hipMemcpyDeviceToHost) == hipSuccess) {
+        std::vector<uint32_t> h(c->wtrace.cap / 4);
+        if (hipMemcpy(h.data(), c->wtrace, c->wtrace.cap, hipMemcpyDeviceToHost) == hipSuccess) {
             if (FILE* fp = fopen(getenv("RV_WAVE_TRACE"), "wb")) { fwrite(h.data(), 4, h.size(), fp); fclose(fp); }
         }
-        hipFree(c->wtrace);
     }
 #endif
-    if (c->gi_stream) { hipStreamSynchronize(c->gi_stream); hipStreamDestroy(c->gi_stream); }
-    hipFree(c->grec_stage); hipFree(c->grec_all); hipFree(c->gring);
-    for (hipEvent_t e : c->gev) if (e) hipEventDestroy(e);
-    if (c->grp_stream) hipStreamDestroy(c->grp_stream);
-    for (BatchSet* bs : {&c->bsets[0], &c->bsets[1], &c->gsets[0], &c->gsets[1]}) {
-        BatchSet& b = *bs;
-        hipFree(b.color); hipFree(b.mv); hipFree(b.depth); hipFree(b.hdist); hipFree(b.hshadow);
-        hipFree(b.tbuf); hipFree(b.gbuf);
-        if (b.rendered) hipEventDestroy(b.rendered);
-        if (b.gathered) hipEventDestroy(b.gathered);
-    }
-    for (hipStream_t fs : c->fstreams) hipStreamDestroy(fs);
-    if (c->comm_stream) hipStreamDestroy(c->comm_stream);
-    if (c->ev_loop) hipEventDestroy(c->ev_loop);
-    if (c->ev_world) hipEventDestroy(c->ev_world);
-    hipFree(c->flow_half); hipFree(c->flow_fb);
-    if (c->ev_spec) hipEventDestroy(c->ev_spec);
-    if (c->ev_flow) hipEventDestroy(c->ev_flow);
-    hipFree(c->cam_dev);
-    if (c->cam_host) hipHostFree(c->cam_host);
-    if (c->cam_ev) hipEventDestroy(c->cam_ev);
-    if (c->ev_gi_done) hipEventDestroy(c->ev_gi_done);
     delete c;
 }
 
@@ -293,7 +240,6 @@ static rv_status begin_frame(rv_ctx* c) {
     const int n = (int)c->slots.size();
     if (n > 1) {
         const int s = (int)(c->frame_seq % (uint64_t)n);
-        slot_save(c);
         slot_load(c, s);
         FrameSlot& sl = c->slots[s];
         // cross-stream waits only: same-stream work is already ordered
@@ -345,13 +291,9 @@ RV_HIDDEN rv_status upload_ids(rv_ctx* c, DevIds& ids, const int32_t* src, int n
     if (changed) *changed = !same;
     if (same) return RV_OK;
     if (rv_status ws = wait_all_frames(c)) return ws;   // frames in flight may read the old list
-    if ((size_t)n > ids.cap || !ids.d) {
+    if ((size_t)n * 4 > ids.d.cap || !ids.d) {
         HIP_TRY(c, c->slots.size() > 1 ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
-        hipFree(ids.d);
-        ids.d = nullptr;
-        ids.cap = 0;
-        HIP_TRY(c, hipMalloc(&ids.d, (size_t)(n > 0 ? n : 1) * 4));
-        ids.cap = (size_t)(n > 0 ? n : 1);
+        if (rv_status s = ids.d.reserve(c, (size_t)(n > 0 ? n : 1) * 4)) return s;
     }
     ids.h.assign(src, src + n);   // the copy reads this stable host buffer
     if (n > 0) HIP_TRY(c, hipMemcpyAsync(ids.d, ids.h.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -370,12 +312,11 @@ rv_status rv_set_frames_in_flight(rv_ctx* c, int32_t n) {
     if (!c || n < 1 || n > 32) return RV_ERR_INVALID;
     if (n > 1 && !c->megakernel) return fail(c, RV_ERR_STATE, "frames in flight need the fused path");
     HIP_TRY(c, hipDeviceSynchronize());
-    slot_save(c);
-    while ((int)c->slots.size() > n) { slot_free(c->slots.back()); c->slots.pop_back(); }
+    c->cur_slot = 0;   // no view of a slot is used until slot_load below
+    while ((int)c->slots.size() > n) c->slots.pop_back();
     while ((int)c->slots.size() < n) {
         c->slots.emplace_back();
         if (!slot_alloc(c, c->slots.back())) {
-            slot_free(c->slots.back());
             c->slots.pop_back();
             slot_load(c, 0);
             return fail(c, RV_ERR_OOM, "frame slot");
@@ -478,8 +419,7 @@ static rv_status tex_table(rv_ctx* c) {
         const size_t later = n_csdf(c) * 2 + c->gi_bytes + 2 * 32 * frame + 8 * W * H + ((size_t)1 << 30);
         if (tb + later > fr || tb > fr / 2) return RV_OK;
     }
-    if (hipMalloc(&c->tex, tb) != hipSuccess) {
-        c->tex = nullptr;
+    if (c->tex.reserve(c, tb)) {   // optional: go without it
         (void)hipGetLastError();
         return RV_OK;
     }
@@ -495,14 +435,14 @@ static rv_status tex_table(rv_ctx* c) {
 // bits.  rv_config.exits_off & RV_EXIT_SKY turns all three exits off (ytop = Y, no horizon, no skip).
 RV_HIDDEN rv_status world_top(rv_ctx* c) {
     c->w.ytop = (uint32_t)c->w.Y;
-    uint32_t* hz = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->brick) + horizon_byte(c->w.coff));
+    uint32_t* hz = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c->brick.p) + horizon_byte(c->w.coff));
     const size_t hzb = horizon_bytes(c->w.X, c->w.Z);
     HIP_TRY(c, hipMemsetAsync(hz, 0xFF, hzb, c->stream));   // no sun exit unless built below
-    int* dt = reinterpret_cast<int*>(reinterpret_cast<char*>(c->brick) + dtop_byte(c->w.coff, c->w.X, c->w.Z));
+    int* dt = reinterpret_cast<int*>(reinterpret_cast<char*>(c->brick.p) + dtop_byte(c->w.coff, c->w.X, c->w.Z));
     HIP_TRY(c, hipMemsetAsync(dt, 0x7F, dtop_bytes(c->w.X, c->w.Z), c->stream));   // no column skip unless built below
     const int off = c->cfg.exits_off;
     if (off & RV_EXIT_SKY) return RV_OK;
-    if (!c->d_top) HIP_TRY(c, hipMalloc(&c->d_top, 4));
+    if (rv_status s = c->d_top.reserve(c, 4)) return s;
     HIP_TRY(c, hipMemsetAsync(c->d_top, 0, 4, c->stream));
     launch_world_top(c->stream, c->brick, current_world(c), c->d_top);
     LAUNCH_CHECK(c);
@@ -511,7 +451,7 @@ RV_HIDDEN rv_status world_top(rv_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->w.ytop = std::min((uint32_t)c->w.Y, top + 1u);   // top = max solid y + 1
     // the column tops: the DDA's empty-column skip (dtop_at; RV_EXIT_COLUMN: off) and the sun horizon's input
-    if (!c->coltop) HIP_TRY(c, hipMalloc(&c->coltop, hzb));
+    if (rv_status s = c->coltop.reserve(c, hzb)) return s;
     HIP_TRY(c, hipMemsetAsync(c->coltop, 0, hzb, c->stream));
     launch_column_tops(c->stream, c->brick, current_world(c), c->coltop, dt);
     LAUNCH_CHECK(c);
@@ -536,15 +476,14 @@ rv_status rv_csdf_build(rv_ctx* c) {
     // Scratch of the three passes: plain allocations, freed after the build completed.  (Stream-
     // ordered hipMallocAsync scratch on the legacy stream was measured to overlap allocations of
     // later contexts' grouped-frame buffers in the same process: sporadically corrupted CSDF.)
-    uint8_t *t0 = nullptr, *t1 = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&t0, n));
-    HIP_TRY(c, hipMalloc((void**)&t1, n));
-    launch_csdf(c->stream, c->brick, current_world(c), t0, t1);
-    LAUNCH_CHECK(c);
-    const hipError_t se = hipStreamSynchronize(c->stream);
-    hipFree(t0);
-    hipFree(t1);
-    HIP_TRY(c, se);
+    {
+        DevBuf<uint8_t> t0, t1;
+        if (rv_status s = t0.reserve(c, n)) return s;
+        if (rv_status s = t1.reserve(c, n)) return s;
+        launch_csdf(c->stream, c->brick, current_world(c), t0, t1);
+        LAUNCH_CHECK(c);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
     return mark_world(c);
 }
 
@@ -590,25 +529,24 @@ rv_status rv_world_import(rv_ctx* c, int32_t kind, const void* host, size_t byte
     if (kind != RV_WORLD_GI) c->geom_ver++;
     if (kind == RV_WORLD_BITS) {
         if (bytes != n_bits_words(c) * 4) return fail(c, RV_ERR_INVALID, "bits size mismatch");
-        uint32_t* d = nullptr;
-        HIP_TRY(c, hipMalloc(&d, bytes));
+        DevBuf<uint32_t> d;
+        if (rv_status s = d.reserve(c, bytes)) return s;
         HIP_TRY(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream));
         launch_bits_import(c->stream, d, c->brick, current_world(c), c->lx, c->ly);
         LAUNCH_CHECK(c);
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(d);
+        d.reset();   // before tex_table looks at the free memory
         persist_mark(c, ColumnRange{0, c->w.X >> 3, 0, c->w.Z >> 3});   // persistence: none of it is the generator's
         if (rv_status ts = world_top(c)) return ts;
         if (rv_status ts = tex_table(c)) return ts;
     } else if (kind == RV_WORLD_CSDF) {
         if (bytes != n_csdf(c)) return fail(c, RV_ERR_INVALID, "csdf size mismatch");
-        uint8_t* d = nullptr;
-        HIP_TRY(c, hipMalloc(&d, bytes));
+        DevBuf<uint8_t> d;
+        if (rv_status s = d.reserve(c, bytes)) return s;
         HIP_TRY(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream));
         launch_csdf_import(c->stream, d, c->brick, current_world(c));
         LAUNCH_CHECK(c);
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(d);
     } else if (kind == RV_WORLD_GI) {
         if (bytes != c->gi_bytes) return fail(c, RV_ERR_INVALID, "gi size mismatch");
         HIP_TRY(c, hipMemcpyAsync(c->gi, host, bytes, hipMemcpyHostToDevice, c->stream));
@@ -624,22 +562,20 @@ rv_status rv_world_export(rv_ctx* c, int32_t kind, void* host, size_t bytes) {
     if (!c || !host) return RV_ERR_INVALID;
     if (kind == RV_WORLD_BITS) {
         if (bytes != n_bits_words(c) * 4) return fail(c, RV_ERR_INVALID, "bits size mismatch");
-        uint32_t* d = nullptr;
-        HIP_TRY(c, hipMalloc(&d, bytes));
+        DevBuf<uint32_t> d;
+        if (rv_status s = d.reserve(c, bytes)) return s;
         launch_bits_export(c->stream, c->brick, d, current_world(c), c->lx, c->ly);
         LAUNCH_CHECK(c);
         HIP_TRY(c, hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(d);
     } else if (kind == RV_WORLD_CSDF) {
         if (bytes != n_csdf(c)) return fail(c, RV_ERR_INVALID, "csdf size mismatch");
-        uint8_t* d = nullptr;
-        HIP_TRY(c, hipMalloc(&d, bytes));
+        DevBuf<uint8_t> d;
+        if (rv_status s = d.reserve(c, bytes)) return s;
         launch_csdf_export(c->stream, c->brick, d, current_world(c));
         LAUNCH_CHECK(c);
         HIP_TRY(c, hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(d);
     } else if (kind == RV_WORLD_GI) {
         if (bytes != c->gi_bytes) return fail(c, RV_ERR_INVALID, "gi size mismatch");
         HIP_TRY(c, hipMemcpyAsync(host, c->gi, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -648,8 +584,8 @@ rv_status rv_world_export(rv_ctx* c, int32_t kind, void* host, size_t bytes) {
         // the exit tables as world_top left them on the device (test hooks)
         const size_t hzb = horizon_bytes(c->w.X, c->w.Z), dtb = dtop_bytes(c->w.X, c->w.Z);
         if (bytes != (kind == RV_WORLD_DTOP ? dtb : hzb)) return fail(c, RV_ERR_INVALID, "exit table size mismatch");
-        const char* src = kind == RV_WORLD_COLTOP ? reinterpret_cast<const char*>(c->coltop)
-                        : reinterpret_cast<const char*>(c->brick) +
+        const char* src = kind == RV_WORLD_COLTOP ? reinterpret_cast<const char*>(c->coltop.p)
+                        : reinterpret_cast<const char*>(c->brick.p) +
                               (kind == RV_WORLD_HORIZON ? horizon_byte(c->w.coff) : dtop_byte(c->w.coff, c->w.X, c->w.Z));
         if (!src) {   // RV_EXIT_SKY off (or no world yet): no column tops were built
             std::memset(host, 0, bytes);
@@ -679,7 +615,7 @@ static rv_status gi_update(rv_ctx* c, uint32_t frame, uint64_t first, uint64_t c
     uint64_t n = n_gi(c);
     if (first >= n) return RV_OK;
     if (first + count > n) count = n - first;
-    if (!c->gi_tmp) HIP_TRY(c, hipMalloc(&c->gi_tmp, c->gi_bytes));
+    if (rv_status s = c->gi_tmp.reserve(c, c->gi_bytes)) return s;
     if (count == n) async = false;   // full sweep flips the double buffer instead
     hipStream_t ks = async ? c->gi_stream : c->stream;
     // the last world/GI write may have been issued on another stream
@@ -720,7 +656,7 @@ rv_status rv_update_gi_data(rv_ctx* c) {
     if (!c) return RV_ERR_INVALID;
     uint64_t rays = c->cfg.gi_rays_per_frame, n = n_gi(c);
     const bool timed = c->timing_n < c->timing_cap;
-    hipEvent_t* e = timed ? &c->ev[(size_t)EV_PER_FRAME * c->timing_n] : nullptr;
+    Event* e = timed ? &c->ev[(size_t)EV_PER_FRAME * c->timing_n] : nullptr;
     c->upd_since_frame = true;
     const uint64_t count = c->gi_offset < n ? std::min(rays, n - c->gi_offset) : 0;
     rv_status s;
@@ -738,8 +674,8 @@ rv_status rv_update_gi_data(rv_ctx* c) {
         s = mark_world(c);
     } else {
         c->spec_gi = false;
-        s = gi_update(c, c->gi_frame, c->gi_offset, rays, c->gi_async, timed ? e[NSTAGE] : nullptr,
-                      timed ? e[NSTAGE + 1] : nullptr);
+        s = gi_update(c, c->gi_frame, c->gi_offset, rays, c->gi_async, timed ? e[NSTAGE].e : nullptr,
+                      timed ? e[NSTAGE + 1].e : nullptr);
     }
     if (s != RV_OK) return s;
     if (timed) c->gi_timed[c->timing_n] = 1;
@@ -768,10 +704,11 @@ static FrameParams make_params(rv_ctx* c, const rv_camera* cam, const float* vp,
     f.color = c->color; f.color_pitch = c->color_pitch;
     f.mv = c->mv; f.mv_pitch = c->mv_pitch;
     f.depth = c->depth; f.depth_pitch = c->depth_pitch;
-    f.hdist = c->hdist; f.hshadow = c->hshadow;
+    const FrameSlot& sl = cur(c);
+    f.hdist = sl.hdist; f.hshadow = sl.hshadow;
     f.counters = c->counters;
     f.sched = c->sched;
-    for (int g = 0; g < 2; g++) { f.chunk_order[g] = c->chunk_order[g]; f.chunk_cost[g] = c->chunk_cost[g]; }
+    for (int g = 0; g < 2; g++) { f.chunk_order[g] = sl.chunk_order[g]; f.chunk_cost[g] = sl.chunk_cost[g]; }
     f.hpos = c->hpos; f.hinfo = c->hinfo; f.hsec = c->hsec; f.pphit = c->pphit;
     for (int q = 0; q < NQUEUE; q++) f.queue_wf[q] = c->wq[q];
     f.qcount = c->qcount;
@@ -804,17 +741,13 @@ RV_HIDDEN rv_status upload_cams(rv_ctx* c, const Seq& q, hipStream_t st, const F
                              const std::function<void(int, FrameCam&)>& fill) {
     const size_t n = (size_t)q.n;
     if (c->cam_pending) HIP_TRY(c, hipEventSynchronize(c->cam_ev));
-    if (n > c->cam_cap) {
+    if (n * sizeof(FrameCam) > std::min(c->cam_dev.cap, c->cam_host.cap)) {
         HIP_TRY(c, hipDeviceSynchronize());   // kernels of earlier calls may still read the old table
-        hipFree(c->cam_dev);
-        if (c->cam_host) hipHostFree(c->cam_host);
-        c->cam_dev = nullptr; c->cam_host = nullptr; c->cam_cap = 0;
-        const size_t cap = std::max<size_t>(n, 256);
-        HIP_TRY(c, hipMalloc(&c->cam_dev, cap * sizeof(FrameCam)));
-        HIP_TRY(c, hipHostMalloc(&c->cam_host, cap * sizeof(FrameCam), hipHostMallocDefault));
-        c->cam_cap = cap;
+        const size_t cap = std::max<size_t>(n, 256) * sizeof(FrameCam);
+        if (rv_status s = c->cam_dev.reserve(c, cap)) return s;
+        if (rv_status s = c->cam_host.reserve(c, cap)) return s;
     }
-    if (!c->cam_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->cam_ev, hipEventDisableTiming));
+    if (rv_status s = c->cam_ev.ensure(c)) return s;
     for (size_t k = 0; k < n; k++) {
         c->cam_host[k] = frame_cam(q.at((int)k));
         if (fill) fill((int)k, c->cam_host[k]);
@@ -836,13 +769,9 @@ static rv_status ensure_queues(rv_ctx* c, FrameParams& f, bool tiles) {
         uint32_t blocks = wf_producer_blocks(f, q, tiles);
         f.qcap[q] = (blocks + NXCD - 1) / NXCD * 256;
         size_t need = (size_t)NXCD * f.qcap[q];
-        if (need > c->wq_cap[q]) {
+        if (need * 4 > c->wq[q].cap) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            hipFree(c->wq[q]);
-            c->wq[q] = nullptr;
-            c->wq_cap[q] = 0;
-            if (hipMalloc(&c->wq[q], need * 4) != hipSuccess) return fail(c, RV_ERR_OOM, "wavefront queues");
-            c->wq_cap[q] = need;
+            if (c->wq[q].reserve(c, need * 4)) return fail(c, RV_ERR_OOM, "wavefront queues");
         }
         f.queue_wf[q] = c->wq[q];
     }
@@ -889,15 +818,16 @@ RV_HIDDEN rv_status run_stages(rv_ctx* c, FrameParams f, bool tiles, int which) 
         // SCHED_COST: re-order the chunks by the wave lifetimes (max over
         // the frames since the last ordering) every order_every frames; a
         // kernel boundary costs ~6 us, the ordering itself ~4 us (both grids' orderings in one launch).
-        if (f.sched == SCHED_COST && ++c->frames_since_order >= (uint32_t)c->order_every) {
-            c->frames_since_order = 0;
+        FrameSlot& sl = cur(c);
+        if (f.sched == SCHED_COST && ++sl.frames_since_order >= (uint32_t)c->order_every) {
+            sl.frames_since_order = 0;
             if (tiles) {
-                launch_chunk_order(c->stream, c->tile_cost, c->tile_order, (uint32_t)f.ntiles,
+                launch_chunk_order(c->stream, sl.tile_cost, sl.tile_order, (uint32_t)f.ntiles,
                                    ((uint32_t)f.ntiles + 7u) & ~7u);
             } else {
-                launch_chunk_order(c->stream, pre ? c->chunk_cost[CG_PREPASS] : nullptr, c->chunk_order[CG_PREPASS],
+                launch_chunk_order(c->stream, pre ? sl.chunk_cost[CG_PREPASS].p : nullptr, sl.chunk_order[CG_PREPASS],
                                    n_chunks(f.hw, f.hh), n_chunks_pad(f.hw, f.hh),
-                                   c->chunk_cost[CG_RENDER], c->chunk_order[CG_RENDER], n_chunks(f.W, f.H),
+                                   sl.chunk_cost[CG_RENDER], sl.chunk_order[CG_RENDER], n_chunks(f.W, f.H),
                                    n_chunks_pad(f.W, f.H));
             }
             LAUNCH_CHECK(c);
@@ -961,15 +891,15 @@ static rv_status flow_frame(rv_ctx* c, FrameParams f) {
     const size_t ntiles = (size_t)ntx * nty;
     if (c->flow_tiles != ntiles || !c->flow_half) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->flow_half);
-        c->flow_half = nullptr; c->flow_tiles = 0;
-        HIP_TRY(c, hipMalloc(&c->flow_half, ntiles * 64 * 8));
+        c->flow_half.reset();
+        c->flow_tiles = 0;
+        if (rv_status s = c->flow_half.reserve(c, ntiles * 64 * 8)) return s;
         HIP_TRY(c, hipMemset(c->flow_half, 0, ntiles * 64 * 8));   // tag 0: no launch's
         c->flow_tiles = ntiles;
         c->flow_epoch = 0;
     }
     if (!c->flow_fb) {
-        HIP_TRY(c, hipMalloc(&c->flow_fb, 8));
+        if (rv_status s = c->flow_fb.reserve(c, 8)) return s;
         HIP_TRY(c, hipMemset(c->flow_fb, 0, 8));
     }
     if (++c->flow_epoch > 0x3FFFFFFFu) {   // 30-bit epochs (tag = epoch << 1 | phase): restart them from a zeroed buffer
@@ -983,7 +913,8 @@ static rv_status flow_frame(rv_ctx* c, FrameParams f) {
                             c->spec_first == first && c->spec_count == count;
     // a full sweep flips the double buffer instead (gi_update); stats frames keep their counters clean
     const bool spec = c->upd_since_frame && !spec_valid && !stats && !c->gi_stats && count > 0 && count < n;
-    if (spec && !c->gi_tmp) HIP_TRY(c, hipMalloc(&c->gi_tmp, c->gi_bytes));
+    if (spec)
+        if (rv_status s = c->gi_tmp.reserve(c, c->gi_bytes)) return s;
     PipeParams p{};
     p.gi_prev = c->gi;
     if (spec) {
@@ -1009,11 +940,9 @@ static rv_status flow_frame(rv_ctx* c, FrameParams f) {
     p.flow_fallback = c->flow_fb;
     if (RV_PIPE_DIAG && getenv("RV_FLOW_WAVE_TRACE")) {   // diagnostics: this launch's per-wave records
         const uint32_t nb = p.len[0] + p.len[1] + p.len[2];
-        if (nb > c->flow_wtrace_n) {
+        if ((size_t)nb * 16 > c->flow_wtrace.cap) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            hipFree(c->flow_wtrace);
-            c->flow_wtrace = nullptr;
-            HIP_TRY(c, hipMalloc(&c->flow_wtrace, (size_t)nb * 16));
+            if (rv_status s = c->flow_wtrace.reserve(c, (size_t)nb * 16)) return s;
         }
         c->flow_wtrace_n = nb;
         c->flow_wlen[0] = p.len[0]; c->flow_wlen[1] = p.len[1]; c->flow_wlen[2] = p.len[2];
@@ -1026,7 +955,7 @@ static rv_status flow_frame(rv_ctx* c, FrameParams f) {
     launch_ref_flow(c->stream, current_world(c), f, p);
     LAUNCH_CHECK(c);
     c->flow_launches++;
-    if (!c->ev_flow) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_flow, hipEventDisableTiming));
+    if (rv_status s = c->ev_flow.ensure(c)) return s;
     HIP_TRY(c, hipEventRecord(c->ev_flow, c->stream));
     if (timed) {
         c->ev_stage[e0 + 1] = -1;
@@ -1035,18 +964,19 @@ static rv_status flow_frame(rv_ctx* c, FrameParams f) {
         c->timing_n++;
     }
     if (spec) {
-        if (!c->ev_spec) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_spec, hipEventDisableTiming));
+        if (rv_status s = c->ev_spec.ensure(c)) return s;
         HIP_TRY(c, hipEventRecord(c->ev_spec, c->stream));
         c->spec_stream = c->stream;
         c->spec_rec = true;
         c->spec_gi = true;
         c->spec_fr = c->gi_frame; c->spec_first = first; c->spec_count = count; c->spec_world = c->world_ver;
     }
-    if (f.sched == SCHED_COST && ++c->frames_since_order >= (uint32_t)c->order_every) {
-        c->frames_since_order = 0;
-        launch_chunk_order(c->stream, c->chunk_cost[CG_PREPASS], c->chunk_order[CG_PREPASS], n_chunks(f.hw, f.hh),
-                           n_chunks_pad(f.hw, f.hh), c->chunk_cost[CG_RENDER],
-                           c->chunk_order[CG_RENDER], n_chunks(f.W, f.H), n_chunks_pad(f.W, f.H));
+    FrameSlot& sl = cur(c);
+    if (f.sched == SCHED_COST && ++sl.frames_since_order >= (uint32_t)c->order_every) {
+        sl.frames_since_order = 0;
+        launch_chunk_order(c->stream, sl.chunk_cost[CG_PREPASS], sl.chunk_order[CG_PREPASS], n_chunks(f.hw, f.hh),
+                           n_chunks_pad(f.hw, f.hh), sl.chunk_cost[CG_RENDER],
+                           sl.chunk_order[CG_RENDER], n_chunks(f.W, f.H), n_chunks_pad(f.W, f.H));
         LAUNCH_CHECK(c);
     }
     return RV_OK;
@@ -1099,25 +1029,23 @@ RV_HIDDEN rv_status tile_list(rv_ctx* c, const int32_t* tile_ids, int32_t ntiles
     rv_status us = upload_ids(c, c->tiles, tile_ids, ntiles, &changed);
     if (us != RV_OK) return us;
     if (changed) c->tiles_ver++;
-    if (c->tiles_seen != c->tiles_ver || tile_px != c->tiles_px) {
+    FrameSlot& sl = cur(c);
+    if (sl.tiles_seen != c->tiles_ver || tile_px != sl.tiles_px) {
         const size_t npad = ((size_t)ntiles + 7) & ~(size_t)7;
-        if (npad > c->tile_ord_cap) {
+        if (npad * 4 > std::min(sl.tile_order.cap, sl.tile_cost.cap)) {
             HIP_TRY(c, c->slots.size() > 1 ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
-            hipFree(c->tile_order); hipFree(c->tile_cost);
-            c->tile_order = nullptr; c->tile_cost = nullptr; c->tile_ord_cap = 0;
-            HIP_TRY(c, hipMalloc(&c->tile_order, npad * 4));
-            HIP_TRY(c, hipMalloc(&c->tile_cost, npad * 4));
-            c->tile_ord_cap = npad;
+            if (rv_status s = sl.tile_order.reserve(c, npad * 4)) return s;
+            if (rv_status s = sl.tile_cost.reserve(c, npad * 4)) return s;
         }
         c->tile_ident.resize(npad);
         for (size_t i = 0; i < npad; i++) c->tile_ident[i] = (int)i;
         if (npad) {
-            HIP_TRY(c, hipMemcpyAsync(c->tile_order, c->tile_ident.data(), npad * 4, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemsetAsync(c->tile_cost, 0, npad * 4, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(sl.tile_order, c->tile_ident.data(), npad * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemsetAsync(sl.tile_cost, 0, npad * 4, c->stream));
         }
-        c->tiles_px = tile_px;
-        c->tiles_seen = c->tiles_ver;
-        c->frames_since_order = 0;
+        sl.tiles_px = tile_px;
+        sl.tiles_seen = c->tiles_ver;
+        sl.frames_since_order = 0;
     }
     return RV_OK;
 }
@@ -1133,27 +1061,23 @@ rv_status rv_frame_tiles(rv_ctx* c, const rv_camera* cam, const float* vp16, con
     for (int i = 0; i < ntiles; i++)
         if (tile_ids[i] < 0 || tile_ids[i] >= tiles_x * tiles_y) return fail(c, RV_ERR_INVALID, "tile id out of range");
     size_t need = (size_t)ntiles * tile_px * tile_px * 4;
-    if (!c->ext_tilebuf && need > c->tilebuf_bytes) {
-        hipFree(c->tilebuf);
-        c->tilebuf = nullptr;
-        HIP_TRY(c, hipMalloc(&c->tilebuf, need));
-        c->tilebuf_bytes = need;
-    }
+    if (!c->ext_tilebuf)
+        if (rv_status s = c->tilebuf.reserve(c, need)) return s;
     if (c->ext_tilebuf && need > c->ext_tilebuf_bytes) return fail(c, RV_ERR_INVALID, "bound tile buffer too small");
     if (rv_status bs = begin_frame(c)) return bs;
     if (rv_status ts = tile_list(c, tile_ids, ntiles, tile_px)) return ts;
     FrameParams f = make_params(c, cam, vp16, pvp16, time, jx, jy, flags);
     f.tiles = c->tiles.d; f.ntiles = ntiles; f.tile_px = tile_px; f.tiles_x = tiles_x;
-    f.tilebuf = c->ext_tilebuf ? c->ext_tilebuf : c->tilebuf;
-    f.chunk_order[CG_RENDER] = c->tile_order; f.chunk_cost[CG_RENDER] = c->tile_cost;
+    f.tilebuf = c->ext_tilebuf ? c->ext_tilebuf : c->tilebuf.p;
+    f.chunk_order[CG_RENDER] = cur(c).tile_order; f.chunk_cost[CG_RENDER] = cur(c).tile_cost;
     if (rv_status rs = run_stages(c, f, true)) return rs;
     return end_frame(c);
 }
 
 rv_status rv_tile_buffer(rv_ctx* c, void** p, size_t* bytes) {
     if (!c || !p) return RV_ERR_INVALID;
-    *p = c->ext_tilebuf ? c->ext_tilebuf : c->tilebuf;
-    if (bytes) *bytes = c->ext_tilebuf ? c->ext_tilebuf_bytes : c->tilebuf_bytes;
+    *p = c->ext_tilebuf ? c->ext_tilebuf : c->tilebuf.p;
+    if (bytes) *bytes = c->ext_tilebuf ? c->ext_tilebuf_bytes : c->tilebuf.cap;
     return RV_OK;
 }
 
@@ -1167,14 +1091,14 @@ rv_status rv_bind_tile_buffer(rv_ctx* c, void* p, size_t bytes) {
 rv_status rv_timing_enable(rv_ctx* c, int32_t max_frames) {
     if (!c || max_frames < 0) return RV_ERR_INVALID;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (hipEvent_t e : c->ev) hipEventDestroy(e);
     c->ev.clear();
     c->timing_cap = 0; c->timing_n = 0;
     c->ev.resize((size_t)max_frames * EV_PER_FRAME);
     c->gi_timed.assign((size_t)max_frames, 0);
     c->ev_stage.assign((size_t)max_frames * EV_PER_FRAME, -1);
     c->ev_used.assign((size_t)max_frames, 0);
-    for (auto& e : c->ev) HIP_TRY(c, hipEventCreate(&e));
+    for (Event& e : c->ev)
+        if (rv_status s = e.ensure(c, hipEventDefault)) return s;
     c->timing_cap = max_frames;
     return RV_OK;
 }
@@ -1185,7 +1109,7 @@ rv_status rv_timing_stages(rv_ctx* c, double* ms, int32_t n, int32_t* frames) {
     for (int k = 0; k < n; k++) ms[k] = 0.0;
     for (int i = 0; i < c->timing_n; i++) {
         const size_t e0 = (size_t)EV_PER_FRAME * i;
-        hipEvent_t* e = &c->ev[e0];
+        const Event* e = &c->ev[e0];
         for (int j = 0; j + 1 < c->ev_used[i]; j++) {
             const int k = c->ev_stage[e0 + j];
             float t = 0.0f;
@@ -1250,19 +1174,19 @@ rv_status rv_bind_output(rv_ctx* c, int32_t kind, void* p, size_t pitch) {
     switch (kind) {
     case RV_IMAGE_COLOR:
         if (p && pitch < W * 4) return fail(c, RV_ERR_INVALID, "pitch too small");
-        c->color = p ? (uint32_t*)p : c->own_color;
+        c->color = p ? (uint32_t*)p : cur(c).own_color.p;
         c->color_pitch = p ? pitch : c->own_color_pitch;
         c->color_ext = p != nullptr;
         return RV_OK;
     case RV_IMAGE_MOTION:
         if (p && pitch < W * 4) return fail(c, RV_ERR_INVALID, "pitch too small");
-        c->mv = p ? (uint32_t*)p : c->own_mv;
+        c->mv = p ? (uint32_t*)p : cur(c).own_mv.p;
         c->mv_pitch = p ? pitch : c->own_mv_pitch;
         c->mv_ext = p != nullptr;
         return RV_OK;
     case RV_IMAGE_DEPTH:
         if (p && pitch < W * 2) return fail(c, RV_ERR_INVALID, "pitch too small");
-        c->depth = p ? (uint16_t*)p : c->own_depth;
+        c->depth = p ? (uint16_t*)p : cur(c).own_depth.p;
         c->depth_pitch = p ? pitch : c->own_depth_pitch;
         c->depth_ext = p != nullptr;
         return RV_OK;
@@ -1278,9 +1202,9 @@ static rv_status image_desc(rv_ctx* c, int32_t kind, void** p, size_t* pitch, si
     case RV_IMAGE_MOTION: *p = c->mv; *pitch = c->mv_pitch; *row_bytes = (size_t)W * 4; *rows = H; return RV_OK;
     case RV_IMAGE_DEPTH: *p = c->depth; *pitch = c->depth_pitch; *row_bytes = (size_t)W * 2; *rows = H; return RV_OK;
     case RV_IMAGE_HALF_DIST:
-        *p = c->hdist; *pitch = (size_t)(W / 2) * 4; *row_bytes = *pitch; *rows = H / 2; return RV_OK;
+        *p = cur(c).hdist; *pitch = (size_t)(W / 2) * 4; *row_bytes = *pitch; *rows = H / 2; return RV_OK;
     case RV_IMAGE_HALF_SHADOW:
-        *p = c->hshadow; *pitch = (size_t)(W / 2) * 4; *row_bytes = *pitch; *rows = H / 2; return RV_OK;
+        *p = cur(c).hshadow; *pitch = (size_t)(W / 2) * 4; *row_bytes = *pitch; *rows = H / 2; return RV_OK;
     default: return fail(c, RV_ERR_INVALID, "bad image kind");
     }
 }
@@ -1310,12 +1234,12 @@ rv_status rv_readback(rv_ctx* c, int32_t kind, void* host, size_t pitch) {
 // variant < 0: rv_trace_rays' kernel; else rv_trace_rays_variant's (validated by the caller)
 static rv_status trace_rays(rv_ctx* c, int32_t variant, const float* org, const float* dir, const float* dist,
                             int64_t n, rv_hit* out) {
-    float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
-    RvHitDev* d_h = nullptr;
-    HIP_TRY(c, hipMalloc(&d_o, (size_t)n * 12));
-    HIP_TRY(c, hipMalloc(&d_d, (size_t)n * 12));
-    HIP_TRY(c, hipMalloc(&d_t, (size_t)n * 4));
-    HIP_TRY(c, hipMalloc(&d_h, (size_t)n * sizeof(RvHitDev)));
+    DevBuf<float> d_o, d_d, d_t;
+    DevBuf<RvHitDev> d_h;
+    if (rv_status s = d_o.reserve(c, (size_t)n * 12)) return s;
+    if (rv_status s = d_d.reserve(c, (size_t)n * 12)) return s;
+    if (rv_status s = d_t.reserve(c, (size_t)n * 4)) return s;
+    if (rv_status s = d_h.reserve(c, (size_t)n * sizeof(RvHitDev))) return s;
     HIP_TRY(c, hipMemcpyAsync(d_o, org, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_t, dist, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -1332,7 +1256,6 @@ static rv_status trace_rays(rv_ctx* c, int32_t variant, const float* org, const 
     LAUNCH_CHECK(c);
     HIP_TRY(c, hipMemcpyAsync(out, d_h, (size_t)n * sizeof(RvHitDev), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    hipFree(d_o); hipFree(d_d); hipFree(d_t); hipFree(d_h);
     return RV_OK;
 }
 

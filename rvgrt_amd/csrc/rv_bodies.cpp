@@ -42,8 +42,8 @@ rv_status rv_world_bodies_move(rv_ctx* c, const rv_body* in, int64_t n, int32_t 
     if (!args_ok(in, n, flags, out)) return fail(c, RV_ERR_INVALID, "rv_world_bodies_move: bad n, flags or array");
     if (n == 0) return RV_OK;
     if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_world_bodies_move before a world build or import");
-    if (rv_status s = dev_reserve(c, c->bodies_in, c->bodies_in_cap, (size_t)n * sizeof(rv_body))) return s;
-    if (rv_status s = dev_reserve(c, c->bodies_out, c->bodies_out_cap, (size_t)n * sizeof(rv_body_out))) return s;
+    if (rv_status s = c->bodies_in.reserve(c, (size_t)n * sizeof(rv_body))) return s;
+    if (rv_status s = c->bodies_out.reserve(c, (size_t)n * sizeof(rv_body_out))) return s;
     HIP_TRY(c, hipMemcpyAsync(c->bodies_in, in, (size_t)n * sizeof(rv_body), hipMemcpyHostToDevice, c->stream));
     if (rv_status s = rv_world_bodies_move_device(c, c->bodies_in, n, flags, c->bodies_out)) return s;
     HIP_TRY(c, hipMemcpyAsync(out, c->bodies_out, (size_t)n * sizeof(rv_body_out), hipMemcpyDeviceToHost, c->stream));

@@ -155,8 +155,8 @@ RV_HIDDEN rv_status comm_group_end(rv_ctx* c, rv_comm* m, hipStream_t s) {
 // One loopback round (see LoopGroup): post, meet, fetch, meet, release.
 static rv_status loop_round(rv_ctx* c, rv_comm* m, hipStream_t s) {
     LoopGroup* g = m->loop;
-    if (!m->ready) HIP_TRY(c, hipEventCreateWithFlags(&m->ready, hipEventDisableTiming));
-    if (!m->done) HIP_TRY(c, hipEventCreateWithFlags(&m->done, hipEventDisableTiming));
+    if (rv_status es = m->ready.ensure(c)) return es;
+    if (rv_status es = m->done.ensure(c)) return es;
     HIP_TRY(c, hipEventRecord(m->ready, s));
     m->pending.ready = m->ready; m->pending.done = m->done;
     {
@@ -279,11 +279,7 @@ void rv_comm_destroy(rv_comm* m) {
         if (ok && !m->aborted && g_rccl.comm_destroy) g_rccl.comm_destroy(m->comm);
         else if (g_rccl.comm_abort) g_rccl.comm_abort(m->comm);   // a peer is gone: do not wait for it
     }
-    if (m->ready) hipEventDestroy(m->ready);
-    if (m->done) hipEventDestroy(m->done);
-    if (m->vdev) hipFree(m->vdev);
-    if (m->vhost) hipHostFree(m->vhost);
-    delete m;
+    delete m;   // with its events and exchange buffers
 }
 
 }  // extern "C"

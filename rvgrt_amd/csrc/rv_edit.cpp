@@ -44,18 +44,16 @@ rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n) {
         n0 = std::max(n0, (size_t)b[i].rs.cells());
         n1 = std::max(n1, (size_t)b[i].rx.cells());
     }
-    if (rv_status s = dev_reserve(c, c->edit_t0, c->edit_t0_cap, n0)) return s;
-    if (rv_status s = dev_reserve(c, c->edit_t1, c->edit_t1_cap, n1)) return s;
+    if (rv_status s = c->edit_t0.reserve(c, n0)) return s;
+    if (rv_status s = c->edit_t1.reserve(c, n1)) return s;
     for (int i = 0; i < n; i++)
         launch_csdf_box(c->stream, c->brick, current_world(c), b[i].rs, b[i].rx, b[i].ry, b[i].rf, c->edit_t0,
                         c->edit_t1);
     LAUNCH_CHECK(c);
     const hipError_t se = hipStreamSynchronize(c->stream);
-    if (c->edit_t0_cap + c->edit_t1_cap > EDIT_SCRATCH_KEEP) {
-        hipFree(c->edit_t0);
-        hipFree(c->edit_t1);
-        c->edit_t0 = c->edit_t1 = nullptr;
-        c->edit_t0_cap = c->edit_t1_cap = 0;
+    if (c->edit_t0.cap + c->edit_t1.cap > EDIT_SCRATCH_KEEP) {
+        c->edit_t0.reset();
+        c->edit_t1.reset();
     }
     HIP_TRY(c, se);
     return RV_OK;
@@ -134,14 +132,8 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
 
     // the bits: boxes to the device (from a stable host copy), one lane per affected word
     c->edit_h.assign(boxes, boxes + n);
-    if (!c->edit_flag) HIP_TRY(c, hipMalloc((void**)&c->edit_flag, 4));
-    if ((size_t)n > c->edit_boxes_cap) {
-        hipFree(c->edit_boxes);
-        c->edit_boxes = nullptr;
-        c->edit_boxes_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->edit_boxes, (size_t)n * sizeof(rv_edit_box)));
-        c->edit_boxes_cap = (size_t)n;
-    }
+    if (rv_status s = c->edit_flag.reserve(c, 4)) return s;
+    if (rv_status s = c->edit_boxes.reserve(c, (size_t)n * sizeof(rv_edit_box))) return s;
     HIP_TRY(c, hipMemcpyAsync(c->edit_boxes, c->edit_h.data(), (size_t)n * sizeof(rv_edit_box), hipMemcpyHostToDevice,
                               c->stream));
     HIP_TRY(c, hipMemsetAsync(c->edit_flag, 0, 4, c->stream));

@@ -36,104 +36,189 @@
 
 using namespace rv;
 
+inline rv_status fail(rv_ctx* c, rv_status s, const std::string& msg);
+
+#define HIP_TRY(ctx, expr)                                                                   \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return fail((ctx), e_ == hipErrorOutOfMemory ? RV_ERR_OOM : RV_ERR_HIP,          \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                  \
+    } while (0)
+
+#define LAUNCH_CHECK(ctx) HIP_TRY(ctx, hipGetLastError())
+
+// ---------------------------------------------------------------- owners
+// Every device buffer, pinned host buffer, event and stream the library creates is a member (or a local) of
+// one of these four move-only types, which are the only places that acquire and release them: what a struct
+// below holds goes with the struct, and rv_destroy is `delete`.  A raw pointer or handle owns nothing.
+
+// A device allocation and its capacity in bytes; converts to the typed pointer.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    void trim(size_t limit) { if (cap > limit) reset(); }
+    // grows to `bytes` (never shrinks; the contents are not kept); empty after a failure
+    rv_status reserve(rv_ctx* c, size_t bytes) {
+        if (bytes <= cap) return RV_OK;
+        reset();
+        HIP_TRY(c, hipMalloc((void**)&p, bytes));
+        cap = bytes;
+        return RV_OK;
+    }
+};
+
+// The same for pinned host memory.
+template <class T>
+struct HostBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    HostBuf() = default;
+    HostBuf(HostBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    HostBuf& operator=(HostBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~HostBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
+    void trim(size_t limit) { if (cap > limit) reset(); }
+    rv_status reserve(rv_ctx* c, size_t bytes) {
+        if (bytes <= cap) return RV_OK;
+        reset();
+        HIP_TRY(c, hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
+        cap = bytes;
+        return RV_OK;
+    }
+};
+
+// An event, created on first use: without timing unless asked (rv_ctx::ev).
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    rv_status ensure(rv_ctx* c, unsigned flags = hipEventDisableTiming) {
+        if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, flags));
+        return RV_OK;
+    }
+};
+
+// A non-blocking stream, created on first use: at the default priority or at a given one.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    rv_status ensure(rv_ctx* c) {
+        if (!s) HIP_TRY(c, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return RV_OK;
+    }
+    rv_status ensure(rv_ctx* c, int prio) {
+        if (!s) HIP_TRY(c, hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio));
+        return RV_OK;
+    }
+};
 
 // Device copy of a host id list, uploaded only when the list changes.
 struct DevIds {
-    int* d = nullptr;
-    size_t cap = 0;
+    DevBuf<int> d;
     std::vector<int32_t> h;
 };
 
 // Per-frame resources of one frame in flight (rv_set_frames_in_flight): the
 // library-owned output images, the half-res pre-pass images and the
-// SCHED_COST order/cost arrays.  The active slot's pointers live in rv_ctx's
-// own fields (slot_load/slot_save swap them), so single-slot code paths read
-// exactly what they did before.
+// SCHED_COST order/cost arrays.  There is one copy of this state: everything
+// reads the active slot through cur(c) = slots[cur_slot], and slot_load only
+// selects the slot and re-points the output views that are not bound.
 struct FrameSlot {
-    uint32_t* own_color = nullptr; uint32_t* own_mv = nullptr; uint16_t* own_depth = nullptr;
-    float* hdist = nullptr; float* hshadow = nullptr;
-    int* chunk_order[2] = {nullptr, nullptr}; uint32_t* chunk_cost[2] = {nullptr, nullptr};
-    int* tile_order = nullptr; uint32_t* tile_cost = nullptr; size_t tile_ord_cap = 0;
-    int tiles_px = 0; uint32_t frames_since_order = 0;
-    uint64_t tiles_seen = ~0ull;
-    hipEvent_t done = nullptr;    // recorded after the slot's last frame work
+    DevBuf<uint32_t> own_color, own_mv; DevBuf<uint16_t> own_depth;
+    DevBuf<float> hdist, hshadow;
+    DevBuf<int> chunk_order[2]; DevBuf<uint32_t> chunk_cost[2];   // SCHED_COST feedback per grid (CG_*)
+    DevBuf<int> tile_order; DevBuf<uint32_t> tile_cost;           // SCHED_COST per tile slot (equal capacities)
+    int tiles_px = 0;             // tile size of the list the order arrays are for
+    uint32_t frames_since_order = 0;
+    uint64_t tiles_seen = ~0ull;  // list version (rv_ctx::tiles_ver) the order arrays are for
+    Event done;                   // recorded after the slot's last frame work
     bool pending = false;         // `done` has been recorded at least once
     hipStream_t last_stream = nullptr;   // stream of the slot's last frame
     uint64_t submitted = 0;       // frame_seq of the slot's last frame
     uint64_t world_seen = 0;      // world version the slot's last frame waited for
-    // rv_render_frames with a tile shard: packed tiles, rank-0 gather buffer
-    uint32_t* tbuf = nullptr; size_t tbytes = 0;
-    uint32_t* gbuf = nullptr; size_t gbytes = 0;
-    hipEvent_t gathered = nullptr;      // recorded on the comm stream after the slot's gather
+    // rv_render_frames with a tile shard: packed tiles, rank-0 gather buffer (sized exactly)
+    DevBuf<uint32_t> tbuf, gbuf;
+    Event gathered;               // recorded on the comm stream after the slot's gather
 };
 
 // rv_render_frames batches: B frames per launch, two sets in ping-pong (set
 // j & 1 also uses frame slot j & 1's scheduling state).
 struct BatchSet {
-    uint32_t* color = nullptr; uint32_t* mv = nullptr; uint16_t* depth = nullptr;
-    float* hdist = nullptr; float* hshadow = nullptr;
-    uint32_t* tbuf = nullptr; uint32_t* gbuf = nullptr;
+    DevBuf<uint32_t> color, mv; DevBuf<uint16_t> depth;
+    DevBuf<float> hdist, hshadow;
+    DevBuf<uint32_t> tbuf, gbuf;
     int nb = 0; size_t slice = 0, gbytes = 0;   // allocated for
-    hipEvent_t rendered = nullptr, gathered = nullptr;
+    Event rendered, gathered;
     bool pending = false;
 };
 
+// Owned: every DevBuf, HostBuf, Event and Stream member.  Not owned: every raw pointer and handle -- `stream`
+// (the caller's, rv_set_stream), color / mv / depth (views of a bound output or of the active slot's image),
+// ext_tilebuf, comm_attached, world_stream, spec_stream and the slots' last_stream.
 struct rv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     rv_config cfg{};
     int lx = 0, ly = 0, lz = 0;
     World w{};
-    uint32_t* d_top = nullptr;     // world_top scratch (one dword)
-    uint32_t* coltop = nullptr;    // sun horizon: highest solid row + 1 per brick column
-    uint32_t* brick = nullptr;
+    DevBuf<uint32_t> d_top;        // world_top scratch (one dword)
+    DevBuf<uint32_t> coltop;       // sun horizon: highest solid row + 1 per brick column
+    DevBuf<uint32_t> brick;
     size_t brick_bytes = 0;
-    uint32_t* gi = nullptr;       // current grid
-    uint32_t* gi_tmp = nullptr;   // update target (double buffer)
+    DevBuf<uint32_t> gi;          // current grid
+    DevBuf<uint32_t> gi_tmp;      // update target (double buffer)
     size_t gi_bytes = 0;
-    uint32_t* atlas = nullptr;
-    uint32_t* tex = nullptr;      // sampleTexture's tile table (World::tex), or null
+    DevBuf<uint32_t> atlas;
+    DevBuf<uint32_t> tex;         // sampleTexture's tile table (World::tex), or empty
     bool tex_tried = false;       // tex_table() ran (the table is built once per context)
-    // frame images (library-owned unless bound)
+    // frame images: the active slot's own ones unless bound
     uint32_t* color = nullptr; size_t color_pitch = 0; bool color_ext = false;
     uint32_t* mv = nullptr; size_t mv_pitch = 0; bool mv_ext = false;
     uint16_t* depth = nullptr; size_t depth_pitch = 0; bool depth_ext = false;
-    uint32_t* own_color = nullptr; uint32_t* own_mv = nullptr; uint16_t* own_depth = nullptr;
     size_t own_color_pitch = 0, own_mv_pitch = 0, own_depth_pitch = 0;
-    float* hdist = nullptr;
-    float* hshadow = nullptr;
-    unsigned long long* counters = nullptr;
+    DevBuf<unsigned long long> counters;
     DevIds tiles;                 // rv_frame_tiles list (device copy, re-uploaded on change)
     DevIds untile_ids;            // rv_untile list
-    int tiles_px = 0;             // tile size of the cached list (active slot)
     uint64_t tiles_ver = 0;       // bumped when the device tile list changes
-    uint64_t tiles_seen = ~0ull;  // list version the active slot's order arrays are for
     std::vector<int> tile_ident;
-    int* tile_order = nullptr; uint32_t* tile_cost = nullptr; size_t tile_ord_cap = 0;   // SCHED_COST per tile slot
-    uint32_t* tilebuf = nullptr; size_t tilebuf_bytes = 0;
+    DevBuf<uint32_t> tilebuf;
     uint32_t* ext_tilebuf = nullptr; size_t ext_tilebuf_bytes = 0;
-    // stage timing (rv_timing_enable): EV_PER_FRAME events per frame
+    // stage timing (rv_timing_enable): EV_PER_FRAME events per frame (created with timing)
     int timing_cap = 0, timing_n = 0;
-    std::vector<hipEvent_t> ev;
+    std::vector<Event> ev;
     std::vector<char> gi_timed;
     std::vector<signed char> ev_stage;   // stage of each frame event slot (-1: end of frame)
     std::vector<int> ev_used;            // frame event slots used per frame
     bool megakernel = true;       // RV_PATH_FUSED (k_prepass/k_render); false: wavefront stages
     // asynchronous GI update (rv_set_gi_async): kernel on gi_stream, copy-back on stream
     bool gi_async = true;
-    hipStream_t gi_stream = nullptr;
+    Stream gi_stream;
     int prio_lo = 0, prio_hi = 0;  // stream priority range (numerically: lo = least urgent)
     int gi_low_prio = 1;           // 1 = GI stream at the lowest priority (fills the frame's gaps)
-    hipEvent_t ev_world = nullptr;    // recorded on `stream` after the last world/GI write
-    hipEvent_t ev_gi_done = nullptr;  // recorded on gi_stream after a GI kernel
+    Event ev_world;               // recorded on `stream` after the last world/GI write
+    Event ev_gi_done;             // recorded on gi_stream after a GI kernel
     int enq = 1;                  // wavefront path: queue append granularity (FrameParams::enq)
     // wavefront buffers
-    float4* hpos = nullptr; uint32_t* hinfo = nullptr; float4* hsec = nullptr; float4* pphit = nullptr;
-    int* wq[NQUEUE] = {nullptr, nullptr, nullptr, nullptr};
-    size_t wq_cap[NQUEUE] = {0, 0, 0, 0};   // items allocated per queue (all sub-queues)
-    unsigned* qcount = nullptr;
-    uint32_t* wtrace = nullptr;   // RV_WAVE_TRACE builds: per-wave records of the last k_render
-    size_t wtrace_bytes = 0;
+    DevBuf<float4> hpos, hsec, pphit; DevBuf<uint32_t> hinfo;
+    DevBuf<int> wq[NQUEUE];       // per queue, all sub-queues
+    DevBuf<unsigned> qcount;
+    DevBuf<uint32_t> wtrace;      // RV_WAVE_TRACE builds: per-wave records of the last k_render
     uint32_t gi_frame = 0;
     uint64_t gi_offset = 0;
     bool world_ready = false;
@@ -147,29 +232,26 @@ struct rv_ctx {
     // latency variant's keep the contiguous order until the option is set (pipe_mix_set)
     uint64_t pipe_mix = PIPE_MIX_DEFAULT, pipe_mix_last = 0;
     bool pipe_mix_set = false;
-    float* pipe_half[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [k & 1] {dist, shadow}
+    DevBuf<float> pipe_half[2][2];   // [k & 1] {dist, shadow}
     bool gi_stats = false;        // rv_set_gi_stats
     // pipelined tile loop: packed tiles / rank-0 gather buffers per frame parity, GI shard staging
-    uint32_t* pipe_tbuf[2] = {nullptr, nullptr}; uint32_t* pipe_gbuf[2] = {nullptr, nullptr};
+    DevBuf<uint32_t> pipe_tbuf[2], pipe_gbuf[2];
     size_t pipe_slice = 0, pipe_gbytes = 0;
-    uint32_t* pipe_gi_stage = nullptr; uint32_t* pipe_gi_all = nullptr;
+    DevBuf<uint32_t> pipe_gi_stage, pipe_gi_all;
     uint64_t pipe_chunk = 0; int pipe_chunk_n = 0;
-    hipEvent_t pipe_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // rendered, all-gathered, gathered[2]
-    uint32_t* pipe_wstat = nullptr;   // env RV_PIPE_WAVE_STATS: per-wave records of the first launches
+    Event pipe_ev[4];             // rendered, all-gathered, gathered[2]
+    DevBuf<uint32_t> pipe_wstat;  // env RV_PIPE_WAVE_STATS: per-wave records of the first launches
     // env RV_FLOW_WAVE_TRACE=<file> (RV_PIPE_DIAG builds): the last flow launch's per-wave records, dumped at
     // rv_destroy (tools/flow_waves.py)
-    uint32_t* flow_wtrace = nullptr; uint32_t flow_wtrace_n = 0, flow_wlen[3] = {0, 0, 0};
+    DevBuf<uint32_t> flow_wtrace; uint32_t flow_wtrace_n = 0, flow_wlen[3] = {0, 0, 0};
     uint32_t pipe_launches = 0;
     uint32_t pipe_wnb[64] = {};       // workgroups of each recorded launch
     int gather_bpp = 3;           // rv_set_gather_bpp: packed pixel bytes of rv_render_frames' tile gather (3 or 4)
-    uint32_t frames_since_order = 0;
-    int* chunk_order[2] = {nullptr, nullptr};      // SCHED_COST feedback per grid (CG_*)
-    uint32_t* chunk_cost[2] = {nullptr, nullptr};
-    std::vector<FrameSlot> slots;  // frames in flight; slots[cur_slot] mirrors the fields above
-    std::vector<hipStream_t> fstreams;   // rv_render_frames: streams of slots 1..n-1 (slot 0: `stream`)
+    std::vector<FrameSlot> slots;  // frames in flight; the active one is slots[cur_slot]
+    std::vector<Stream> fstreams;  // rv_render_frames: streams of slots 1..n-1 (slot 0: `stream`)
     int fstream_prio = 0;
-    hipStream_t comm_stream = nullptr;   // rv_render_frames: RCCL gathers, in frame order
-    hipEvent_t ev_loop = nullptr;        // scratch event of rv_render_frames
+    Stream comm_stream;           // rv_render_frames: RCCL gathers, in frame order
+    Event ev_loop;                // scratch event of rv_render_frames
     BatchSet bsets[2];
     int batch_streams = 1;               // RV_OPT_BATCH_STREAMS: streams rv_render_frames' groups alternate over
     // rv_set_tile_shard: this rank's tiles and the gathered layout (rank 0)
@@ -190,10 +272,10 @@ struct rv_ctx {
     // launch per frame.  Tile-major half-res hand-off buffer, per-tile flags, the launch epoch and the
     // count of render waves that fell back to evaluating their window.
     int flow = 1;
-    unsigned long long* flow_half = nullptr; size_t flow_tiles = 0;
+    DevBuf<unsigned long long> flow_half; size_t flow_tiles = 0;
     uint32_t flow_epoch = 0;
-    unsigned long long* flow_fb = nullptr;
-    hipEvent_t ev_flow = nullptr;   // recorded after every flow launch, on the stream it ran on
+    DevBuf<unsigned long long> flow_fb;
+    Event ev_flow;                  // recorded after every flow launch, on the stream it ran on
     uint64_t flow_launches = 0;
     // RV_OPT_GI_PAIRS: latency-variant launches trace a GI cell's two rays on a lane pair (1 all, 0 none);
     // default -1: a rank's tile share only -- its GI part is 1/N of the cells and its longest GI waves
@@ -209,39 +291,39 @@ struct rv_ctx {
     // (the caller runs renderLoop's per-frame update, so the next one is worth computing ahead).
     bool spec_gi = false;
     uint32_t spec_fr = 0; uint64_t spec_first = 0, spec_count = 0, spec_world = 0;
-    hipEvent_t ev_spec = nullptr; hipStream_t spec_stream = nullptr; bool spec_rec = false;
+    Event ev_spec; hipStream_t spec_stream = nullptr; bool spec_rec = false;
     bool upd_since_frame = false;
     // grouped reference frames (rv_set_frame_group): frame sets per group parity, phase-A records
     // (this rank's stage slots and the all-gathered ones, 3 groups each), the update ring, the
     // phase-B stream and the loop's events
     int group = 0;
     BatchSet gsets[2];
-    uint2* grec_stage = nullptr; uint2* grec_all = nullptr; size_t grec_stage_n = 0, grec_all_n = 0;
-    uint32_t* gring = nullptr; size_t gring_n = 0;
-    hipStream_t grp_stream = nullptr;
-    hipEvent_t gev[8] = {};
+    DevBuf<uint2> grec_stage, grec_all;
+    DevBuf<uint32_t> gring;
+    Stream grp_stream;
+    Event gev[8];
     rv_comm* comm_attached = nullptr;   // the communicator of the last rv_render_frame_seq (bounded rv_sync)
     float shard_w0 = 1.0f;              // rank 0's tile weight of the shard (rv_set_tile_shard_weighted)
     // per-frame camera table of batched launches (rv_render_frame_seq): device copy, pinned staging
-    FrameCam* cam_dev = nullptr; FrameCam* cam_host = nullptr; size_t cam_cap = 0;
-    hipEvent_t cam_ev = nullptr; bool cam_pending = false;
+    DevBuf<FrameCam> cam_dev; HostBuf<FrameCam> cam_host;   // equal capacities
+    Event cam_ev; bool cam_pending = false;
     uint64_t gi_swapped_at = 0;    // frame_seq at the last GI buffer flip: older frames read gi_tmp
     hipStream_t world_stream = nullptr;   // stream ev_world was recorded on
     // rv_world_edit: the boxes' device copy (and the stable host copy it is uploaded from), the
     // "a word changed" flag, the local CSDF passes' scratch (kept while small) and rv_world_edit_info's record
     std::vector<rv_edit_box> edit_h;
-    rv_edit_box* edit_boxes = nullptr; size_t edit_boxes_cap = 0;
-    uint32_t* edit_flag = nullptr;
-    uint8_t* edit_t0 = nullptr; uint8_t* edit_t1 = nullptr; size_t edit_t0_cap = 0, edit_t1_cap = 0;
+    DevBuf<rv_edit_box> edit_boxes;
+    DevBuf<uint32_t> edit_flag;
+    DevBuf<uint8_t> edit_t0, edit_t1;
     uint64_t edit_count = 0, edit_cells = 0; int edit_full = 0;
-    // rv_gi_relight: the steps' records and the box's two dense value arrays (kept between calls; caps in bytes),
+    // rv_gi_relight: the steps' records and the box's two dense value arrays (kept between calls),
     // rv_gi_relight_info's sums
-    uint2* relight_rec = nullptr; size_t relight_rec_cap = 0;
-    uint32_t* relight_dense[2] = {nullptr, nullptr}; size_t relight_dense_cap[2] = {0, 0};
+    DevBuf<uint2> relight_rec;
+    DevBuf<uint32_t> relight_dense[2];
     uint64_t relight_calls = 0, relight_cells = 0, relight_records = 0;
     // rv_world_scroll: the scratch copy of the retained records (freed after a call when above the edit
     // scratch's keep limit) and rv_world_scroll_info's record; the window's origin is cfg.seed_x / seed_z
-    void* scroll_tmp = nullptr; size_t scroll_tmp_cap = 0;
+    DevBuf<void> scroll_tmp;
     uint64_t scroll_count = 0, scroll_cells = 0; int scroll_full = 0;
     bool tex_follow = false;       // rv_texture_follow_scroll: a scroll adds its step to w.tex_ox / tex_oz
     // rv_world_persist (rv_persist.cpp).  A column's key is (wz, wx), the terrain coordinate of its low corner,
@@ -253,14 +335,14 @@ struct rv_ctx {
     bool persist = false;
     std::set<std::pair<int32_t, int32_t>> persist_dirty;
     std::map<std::pair<int32_t, int32_t>, std::vector<uint32_t>> persist_store;
-    int2* persist_cols = nullptr; size_t persist_cols_cap = 0;
-    uint32_t* persist_stage = nullptr; size_t persist_stage_cap = 0;
+    DevBuf<int2> persist_cols;
+    DevBuf<uint32_t> persist_stage;
     std::vector<int2> persist_cols_h;
-    uint32_t* persist_stage_h = nullptr; size_t persist_stage_h_cap = 0;   // pinned: the two 1-MiB copies of a C4 step
+    HostBuf<uint32_t> persist_stage_h;   // pinned: the two 1-MiB copies of a C4 step
     uint64_t persist_captured = 0, persist_restored = 0;
-    // rv_world_bodies_move (rv_bodies.cpp): the host form's device copies of its arrays (kept between calls;
-    // caps in bytes) and rv_world_bodies_info's sums
-    void* bodies_in = nullptr; void* bodies_out = nullptr; size_t bodies_in_cap = 0, bodies_out_cap = 0;
+    // rv_world_bodies_move (rv_bodies.cpp): the host form's device copies of its arrays (kept between calls)
+    // and rv_world_bodies_info's sums
+    DevBuf<void> bodies_in, bodies_out;
     uint64_t bodies_calls = 0, bodies_moved = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
@@ -328,13 +410,13 @@ struct rv_comm {
     rv_ctx* ctx = nullptr;       // the context it was created with (bounded waits, rv_comm_destroy)
     bool in_group = false;
     LoopGroup::Post pending;     // loopback: the ops of the open group
-    hipEvent_t ready = nullptr, done = nullptr;
+    Event ready, done;           // loopback: this rank's events of a round
     uint64_t verified = 0;       // config record the ranks last agreed on (shard / bpp)
     bool aborted = false;
     // verify_ranks' exchange buffers, allocated on first use and kept: (nranks + 1) x 8 B on the device
     // (the all-gather's output, then this rank's hash), nranks x 8 B pinned on the host
-    uint64_t* vdev = nullptr;
-    uint64_t* vhost = nullptr;
+    DevBuf<uint64_t> vdev;
+    HostBuf<uint64_t> vhost;
 };
 
 
@@ -347,52 +429,17 @@ inline rv_status fail(rv_ctx* c, rv_status s, const std::string& msg) {
     return s;
 }
 
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return fail((ctx), e_ == hipErrorOutOfMemory ? RV_ERR_OOM : RV_ERR_HIP,          \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                  \
-    } while (0)
-
-#define LAUNCH_CHECK(ctx) HIP_TRY(ctx, hipGetLastError())
-
-// Grows a device array the context keeps between calls to `need` bytes (its contents are not kept).
-template <class T>
-inline rv_status dev_reserve(rv_ctx* c, T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return RV_OK;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&p, need));
-    cap = need;
-    return RV_OK;
-}
-
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-inline void slot_save(rv_ctx* c) {
-    FrameSlot& sl = c->slots[c->cur_slot];
-    sl.own_color = c->own_color; sl.own_mv = c->own_mv; sl.own_depth = c->own_depth;
-    sl.hdist = c->hdist; sl.hshadow = c->hshadow;
-    for (int g = 0; g < 2; g++) { sl.chunk_order[g] = c->chunk_order[g]; sl.chunk_cost[g] = c->chunk_cost[g]; }
-    sl.tile_order = c->tile_order; sl.tile_cost = c->tile_cost; sl.tile_ord_cap = c->tile_ord_cap;
-    sl.tiles_px = c->tiles_px; sl.frames_since_order = c->frames_since_order;
-    sl.tiles_seen = c->tiles_seen;
-}
+inline FrameSlot& cur(rv_ctx* c) { return c->slots[c->cur_slot]; }   // the active slot
 
+// Selects the active slot: the output views that are not bound follow it.
 inline void slot_load(rv_ctx* c, int s) {
-    const FrameSlot& sl = c->slots[s];
     c->cur_slot = s;
-    c->own_color = sl.own_color; c->own_mv = sl.own_mv; c->own_depth = sl.own_depth;
+    const FrameSlot& sl = c->slots[s];
     if (!c->color_ext) c->color = sl.own_color;
     if (!c->mv_ext) c->mv = sl.own_mv;
     if (!c->depth_ext) c->depth = sl.own_depth;
-    c->hdist = sl.hdist; c->hshadow = sl.hshadow;
-    for (int g = 0; g < 2; g++) { c->chunk_order[g] = sl.chunk_order[g]; c->chunk_cost[g] = sl.chunk_cost[g]; }
-    c->tile_order = sl.tile_order; c->tile_cost = sl.tile_cost; c->tile_ord_cap = sl.tile_ord_cap;
-    c->tiles_px = sl.tiles_px; c->frames_since_order = sl.frames_since_order;
-    c->tiles_seen = sl.tiles_seen;
 }
 
 // Images (rows padded to 256 B like a D3D12 placed footprint), half-res
@@ -400,10 +447,8 @@ inline void slot_load(rv_ctx* c, int s) {
 inline bool slot_alloc(rv_ctx* c, FrameSlot& sl) {
     const int W = c->cfg.width, H = c->cfg.height;
     const size_t hbytes = (size_t)(W / 2) * (H / 2) * 4;
-    if (hipMalloc(&sl.own_color, c->own_color_pitch * H) != hipSuccess ||
-        hipMalloc(&sl.own_mv, c->own_mv_pitch * H) != hipSuccess ||
-        hipMalloc(&sl.own_depth, c->own_depth_pitch * H) != hipSuccess ||
-        hipMalloc(&sl.hdist, hbytes) != hipSuccess || hipMalloc(&sl.hshadow, hbytes) != hipSuccess)
+    if (sl.own_color.reserve(c, c->own_color_pitch * H) || sl.own_mv.reserve(c, c->own_mv_pitch * H) ||
+        sl.own_depth.reserve(c, c->own_depth_pitch * H) || sl.hdist.reserve(c, hbytes) || sl.hshadow.reserve(c, hbytes))
         return false;
     hipMemset(sl.own_color, 0, c->own_color_pitch * H);
     hipMemset(sl.own_mv, 0, c->own_mv_pitch * H);
@@ -415,24 +460,11 @@ inline bool slot_alloc(rv_ctx* c, FrameSlot& sl) {
         uint32_t npad = n_chunks_pad(nb[g][0], nb[g][1]);
         std::vector<int> id(npad);
         for (uint32_t i = 0; i < npad; i++) id[i] = (int)i;
-        if (hipMalloc(&sl.chunk_order[g], npad * 4) != hipSuccess || hipMalloc(&sl.chunk_cost[g], npad * 4) != hipSuccess)
-            return false;
+        if (sl.chunk_order[g].reserve(c, npad * 4) || sl.chunk_cost[g].reserve(c, npad * 4)) return false;
         hipMemcpy(sl.chunk_order[g], id.data(), npad * 4, hipMemcpyHostToDevice);
         hipMemset(sl.chunk_cost[g], 0, npad * 4);
     }
-    return hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&sl.gathered, hipEventDisableTiming) == hipSuccess;
-}
-
-inline void slot_free(FrameSlot& sl) {
-    hipFree(sl.own_color); hipFree(sl.own_mv); hipFree(sl.own_depth);
-    hipFree(sl.hdist); hipFree(sl.hshadow);
-    for (int g = 0; g < 2; g++) { hipFree(sl.chunk_order[g]); hipFree(sl.chunk_cost[g]); }
-    hipFree(sl.tile_order); hipFree(sl.tile_cost);
-    hipFree(sl.tbuf); hipFree(sl.gbuf);
-    if (sl.done) hipEventDestroy(sl.done);
-    if (sl.gathered) hipEventDestroy(sl.gathered);
-    sl = FrameSlot{};
+    return sl.done.ensure(c) == RV_OK && sl.gathered.ensure(c) == RV_OK;
 }
 
 // per frame: [0, NSTAGE-1) start of each frame stage, [NSTAGE-1] end of the

@@ -10,19 +10,18 @@ static rv_status bset_alloc(rv_ctx* c, BatchSet& b, int B, size_t slice, size_t 
     const int H = c->cfg.height, W = c->cfg.width;
     const size_t hbytes = (size_t)(W / 2) * (H / 2) * 4;
     HIP_TRY(c, hipDeviceSynchronize());
-    hipFree(b.color); hipFree(b.mv); hipFree(b.depth); hipFree(b.hdist); hipFree(b.hshadow);
-    hipFree(b.tbuf); hipFree(b.gbuf);
-    b.color = nullptr; b.mv = nullptr; b.depth = nullptr; b.hdist = b.hshadow = nullptr;
-    b.tbuf = b.gbuf = nullptr; b.nb = 0; b.pending = false;
-    HIP_TRY(c, hipMalloc(&b.color, c->own_color_pitch * H * B));
-    HIP_TRY(c, hipMalloc(&b.mv, c->own_mv_pitch * H * B));
-    HIP_TRY(c, hipMalloc(&b.depth, c->own_depth_pitch * H * B));
-    HIP_TRY(c, hipMalloc(&b.hdist, hbytes * B));
-    HIP_TRY(c, hipMalloc(&b.hshadow, hbytes * B));
-    if (slice) HIP_TRY(c, hipMalloc(&b.tbuf, slice * B));
-    if (gneed) HIP_TRY(c, hipMalloc(&b.gbuf, gneed));
-    if (!b.rendered) HIP_TRY(c, hipEventCreateWithFlags(&b.rendered, hipEventDisableTiming));
-    if (!b.gathered) HIP_TRY(c, hipEventCreateWithFlags(&b.gathered, hipEventDisableTiming));
+    b.color.reset(); b.mv.reset(); b.depth.reset(); b.hdist.reset(); b.hshadow.reset();
+    b.tbuf.reset(); b.gbuf.reset();
+    b.nb = 0; b.pending = false;
+    if (rv_status s = b.color.reserve(c, c->own_color_pitch * H * B)) return s;
+    if (rv_status s = b.mv.reserve(c, c->own_mv_pitch * H * B)) return s;
+    if (rv_status s = b.depth.reserve(c, c->own_depth_pitch * H * B)) return s;
+    if (rv_status s = b.hdist.reserve(c, hbytes * B)) return s;
+    if (rv_status s = b.hshadow.reserve(c, hbytes * B)) return s;
+    if (rv_status s = b.tbuf.reserve(c, slice * B)) return s;   // none without a shard
+    if (rv_status s = b.gbuf.reserve(c, gneed)) return s;       // rank 0 only
+    if (rv_status s = b.rendered.ensure(c)) return s;
+    if (rv_status s = b.gathered.ensure(c)) return s;
     b.nb = B; b.slice = slice; b.gbytes = gneed;
     return RV_OK;
 }
@@ -33,16 +32,16 @@ static rv_status bset_publish(rv_ctx* c, const BatchSet& lb, size_t li, bool all
     const int W = c->cfg.width, H = c->cfg.height;
     const size_t hbytes = (size_t)(W / 2) * (H / 2) * 4;
     const size_t cstride = c->own_color_pitch * H, mstride = c->own_mv_pitch * H, dstride = c->own_depth_pitch * H;
-    HIP_TRY(c, hipMemcpy2DAsync(c->color, c->color_pitch, reinterpret_cast<const char*>(lb.color) + li * cstride,
+    HIP_TRY(c, hipMemcpy2DAsync(c->color, c->color_pitch, reinterpret_cast<const char*>(lb.color.p) + li * cstride,
                                 c->own_color_pitch, (size_t)W * 4, H, hipMemcpyDeviceToDevice, st));
     if (!all) return RV_OK;
-    HIP_TRY(c, hipMemcpy2DAsync(c->mv, c->mv_pitch, reinterpret_cast<const char*>(lb.mv) + li * mstride,
+    HIP_TRY(c, hipMemcpy2DAsync(c->mv, c->mv_pitch, reinterpret_cast<const char*>(lb.mv.p) + li * mstride,
                                 c->own_mv_pitch, (size_t)W * 4, H, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpy2DAsync(c->depth, c->depth_pitch, reinterpret_cast<const char*>(lb.depth) + li * dstride,
+    HIP_TRY(c, hipMemcpy2DAsync(c->depth, c->depth_pitch, reinterpret_cast<const char*>(lb.depth.p) + li * dstride,
                                 c->own_depth_pitch, (size_t)W * 2, H, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->hdist, reinterpret_cast<const char*>(lb.hdist) + li * hbytes, hbytes,
+    HIP_TRY(c, hipMemcpyAsync(cur(c).hdist, reinterpret_cast<const char*>(lb.hdist.p) + li * hbytes, hbytes,
                               hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->hshadow, reinterpret_cast<const char*>(lb.hshadow) + li * hbytes, hbytes,
+    HIP_TRY(c, hipMemcpyAsync(cur(c).hshadow, reinterpret_cast<const char*>(lb.hshadow.p) + li * hbytes, hbytes,
                               hipMemcpyDeviceToDevice, st));
     return RV_OK;
 }
@@ -60,7 +59,6 @@ static rv_status render_gi_groups(rv_ctx* c, const Seq& q, int32_t flags, hipStr
     const size_t cstride = c->own_color_pitch * H, mstride = c->own_mv_pitch * H, dstride = c->own_depth_pitch * H;
     BatchSet& bs = c->bsets[0];
     if (rv_status as = bset_alloc(c, bs, B, bs.slice, bs.gbytes)) return as;
-    slot_save(c);
     slot_load(c, 0);
     c->stream = S;
     if (rv_status ws = wait_all_frames(c)) return ws;   // frames of earlier calls, the last world write
@@ -78,11 +76,11 @@ static rv_status render_gi_groups(rv_ctx* c, const Seq& q, int32_t flags, hipStr
         for (int j = 0; j < nb; j++) {
             if (rv_status gs = rv_update_gi_data(c)) return gs;
             FrameParams g = make_params_d(c, q.at(done + j), flags);
-            g.hdist = reinterpret_cast<float*>(reinterpret_cast<char*>(bs.hdist) + (size_t)j * hbytes);
-            g.hshadow = reinterpret_cast<float*>(reinterpret_cast<char*>(bs.hshadow) + (size_t)j * hbytes);
-            g.color = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bs.color) + (size_t)j * cstride);
-            g.mv = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bs.mv) + (size_t)j * mstride);
-            g.depth = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(bs.depth) + (size_t)j * dstride);
+            g.hdist = reinterpret_cast<float*>(reinterpret_cast<char*>(bs.hdist.p) + (size_t)j * hbytes);
+            g.hshadow = reinterpret_cast<float*>(reinterpret_cast<char*>(bs.hshadow.p) + (size_t)j * hbytes);
+            g.color = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bs.color.p) + (size_t)j * cstride);
+            g.mv = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(bs.mv.p) + (size_t)j * mstride);
+            g.depth = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(bs.depth.p) + (size_t)j * dstride);
             g.color_pitch = c->own_color_pitch; g.mv_pitch = c->own_mv_pitch; g.depth_pitch = c->own_depth_pitch;
             if (rv_status rs = run_stages(c, g, false, 2)) return rs;
             c->frame_seq++;
@@ -146,30 +144,28 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
     const uint64_t chunk = shard_gi ? (rays + N - 1) / N : 0;   // GI cells per rank (all-gather unit)
     for (auto& ph : c->pipe_half)
         for (int q2 = 0; q2 < 2; q2++)
-            if (!ph[q2]) HIP_TRY(c, hipMalloc(&ph[q2], hbytes));
-    if (!c->gi_tmp) HIP_TRY(c, hipMalloc(&c->gi_tmp, c->gi_bytes));
+            if (rv_status s = ph[q2].reserve(c, hbytes)) return s;
+    if (rv_status s = c->gi_tmp.reserve(c, c->gi_bytes)) return s;
     if (tiles && (c->pipe_slice != slice || c->pipe_gbytes != (root ? slice * N : 0))) {
         HIP_TRY(c, hipDeviceSynchronize());
         for (int b = 0; b < 2; b++) {
-            hipFree(c->pipe_tbuf[b]); hipFree(c->pipe_gbuf[b]);
-            c->pipe_tbuf[b] = nullptr; c->pipe_gbuf[b] = nullptr;
-            HIP_TRY(c, hipMalloc(&c->pipe_tbuf[b], slice ? slice : 1));
-            if (root) HIP_TRY(c, hipMalloc(&c->pipe_gbuf[b], slice * N));
+            c->pipe_tbuf[b].reset(); c->pipe_gbuf[b].reset();
+            if (rv_status s = c->pipe_tbuf[b].reserve(c, slice ? slice : 1)) return s;
+            if (root)
+                if (rv_status s = c->pipe_gbuf[b].reserve(c, slice * N)) return s;
         }
         c->pipe_slice = slice; c->pipe_gbytes = root ? slice * N : 0;
     }
     if (shard_gi && (c->pipe_chunk != chunk || c->pipe_chunk_n != N)) {
         HIP_TRY(c, hipDeviceSynchronize());
-        hipFree(c->pipe_gi_stage); hipFree(c->pipe_gi_all);
-        c->pipe_gi_stage = nullptr; c->pipe_gi_all = nullptr;
+        c->pipe_gi_stage.reset(); c->pipe_gi_all.reset();
         c->carry_gi = false;   // the kept shard lived in the old stage buffer
-        HIP_TRY(c, hipMalloc(&c->pipe_gi_stage, chunk * 4));
-        HIP_TRY(c, hipMalloc(&c->pipe_gi_all, chunk * N * 4));
+        if (rv_status s = c->pipe_gi_stage.reserve(c, chunk * 4)) return s;
+        if (rv_status s = c->pipe_gi_all.reserve(c, chunk * N * 4)) return s;
         c->pipe_chunk = chunk; c->pipe_chunk_n = N;
     }
-    for (hipEvent_t& e : c->pipe_ev)
-        if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    slot_save(c);
+    for (Event& e : c->pipe_ev)
+        if (rv_status s = e.ensure(c)) return s;
     slot_load(c, 0);
     c->stream = S;
     if (rv_status ws = wait_all_frames(c)) return ws;   // frames of earlier calls, the last world write
@@ -211,7 +207,7 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
         if (!tiles) return;
         f.tiles = c->tiles.d; f.ntiles = (int)c->shard_ids.size(); f.tile_px = T; f.tiles_x = (W + T - 1) / T;
         f.tilebuf = c->pipe_tbuf[k & 1]; f.tile_bpp = bpp;
-        f.chunk_order[CG_RENDER] = c->tile_order; f.chunk_cost[CG_RENDER] = c->tile_cost;
+        f.chunk_order[CG_RENDER] = cur(c).tile_order; f.chunk_cost[CG_RENDER] = cur(c).tile_cost;
     };
     const World w = current_world(c);
     unsigned long long* cnt_gi = c->counters + (size_t)ST_GI * NCNT;
@@ -292,7 +288,7 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
         pipe_dispatch(p, c->pipe_order, c->pipe_mix_last, lens);
         if (RV_PIPE_DIAG && getenv("RV_PIPE_WAVE_STATS") && more) {   // diagnostics: summarised by rv_destroy
             const uint32_t nb = p.len[0] + p.len[1] + p.len[2];
-            if (!c->pipe_wstat) HIP_TRY(c, hipMalloc(&c->pipe_wstat, (size_t)PIPE_WSTAT_N * PIPE_WSTAT_MAXB * 4));
+            if (rv_status s = c->pipe_wstat.reserve(c, (size_t)PIPE_WSTAT_N * PIPE_WSTAT_MAXB * 4)) return s;
             if (c->pipe_launches < PIPE_WSTAT_N && nb <= PIPE_WSTAT_MAXB) {
                 p.wave_max = c->pipe_wstat + (size_t)c->pipe_launches * PIPE_WSTAT_MAXB;
                 HIP_TRY(c, hipMemsetAsync(p.wave_max, 0xFF, (size_t)nb * 4, S));
@@ -331,7 +327,7 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
             if (rv_status gs = comm_group_start(c, comm)) return gs;
             if (root) {
                 for (int r = 1; r < N; r++)
-                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(c->pipe_gbuf[k & 1]) + (size_t)r * slice,
+                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(c->pipe_gbuf[k & 1].p) + (size_t)r * slice,
                                                  slice, r, c->comm_stream))
                         return rs;
             } else {
@@ -360,14 +356,15 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
             c->carry_geom = c->geom_ver;
             pp_key(c, q.after(), flags, c->carry_key);
         }
-        if (f.sched == SCHED_COST && ++c->frames_since_order >= (uint32_t)c->order_every) {
-            c->frames_since_order = 0;
+        FrameSlot& sl = cur(c);
+        if (f.sched == SCHED_COST && ++sl.frames_since_order >= (uint32_t)c->order_every) {
+            sl.frames_since_order = 0;
             if (tiles) {
-                launch_chunk_order(S, c->tile_cost, c->tile_order, (uint32_t)f.ntiles, ((uint32_t)f.ntiles + 7u) & ~7u);
+                launch_chunk_order(S, sl.tile_cost, sl.tile_order, (uint32_t)f.ntiles, ((uint32_t)f.ntiles + 7u) & ~7u);
             } else {
-                launch_chunk_order(S, c->chunk_cost[CG_PREPASS], c->chunk_order[CG_PREPASS], n_chunks(f.hw, f.hh),
-                                   n_chunks_pad(f.hw, f.hh), c->chunk_cost[CG_RENDER],
-                                   c->chunk_order[CG_RENDER], n_chunks(f.W, f.H), n_chunks_pad(f.W, f.H));
+                launch_chunk_order(S, sl.chunk_cost[CG_PREPASS], sl.chunk_order[CG_PREPASS], n_chunks(f.hw, f.hh),
+                                   n_chunks_pad(f.hw, f.hh), sl.chunk_cost[CG_RENDER],
+                                   sl.chunk_order[CG_RENDER], n_chunks(f.W, f.H), n_chunks_pad(f.W, f.H));
             }
             LAUNCH_CHECK(c);
         }
@@ -381,8 +378,8 @@ static rv_status render_gi_pipe(rv_ctx* c, const Seq& q, int32_t flags, hipStrea
     }
     // the last frame's half-res images become the slot's (rv_readback)
     const int lk = half(frames - 1);
-    HIP_TRY(c, hipMemcpyAsync(c->hdist, c->pipe_half[lk][0], hbytes, hipMemcpyDeviceToDevice, S));
-    HIP_TRY(c, hipMemcpyAsync(c->hshadow, c->pipe_half[lk][1], hbytes, hipMemcpyDeviceToDevice, S));
+    HIP_TRY(c, hipMemcpyAsync(cur(c).hdist, c->pipe_half[lk][0], hbytes, hipMemcpyDeviceToDevice, S));
+    HIP_TRY(c, hipMemcpyAsync(cur(c).hshadow, c->pipe_half[lk][1], hbytes, hipMemcpyDeviceToDevice, S));
     if (rv_status ms = mark_world(c)) return ms;
     c->carry_world = c->world_ver;   // the kept update is valid until the next world/GI write
     FrameSlot& s0 = c->slots[0];
@@ -436,30 +433,24 @@ static rv_status render_gi_group(rv_ctx* c, const Seq& q, int32_t flags, hipStre
     for (BatchSet& b : c->gsets)
         if (rv_status as = bset_alloc(c, b, F, tiles ? slice : 0, gneed)) return as;
     const size_t nstage = 3 * (size_t)F * chunk, nall = 3 * (size_t)Nrec * F * chunk;
-    if (c->grec_stage_n < nstage || c->grec_all_n < nall || c->gring_n < cap) {
+    if (c->grec_stage.cap < nstage * sizeof(uint2) || c->grec_all.cap < nall * sizeof(uint2) ||
+        c->gring.cap < cap * 4) {
         HIP_TRY(c, hipDeviceSynchronize());
-        hipFree(c->grec_stage); hipFree(c->grec_all); hipFree(c->gring);
-        c->grec_stage = nullptr; c->grec_all = nullptr; c->gring = nullptr;
-        c->grec_stage_n = c->grec_all_n = c->gring_n = 0;
-        HIP_TRY(c, hipMalloc(&c->grec_stage, nstage * sizeof(uint2)));
-        HIP_TRY(c, hipMalloc(&c->grec_all, nall * sizeof(uint2)));
-        HIP_TRY(c, hipMalloc(&c->gring, cap * 4));
-        c->grec_stage_n = nstage; c->grec_all_n = nall; c->gring_n = cap;
+        c->grec_stage.reset(); c->grec_all.reset(); c->gring.reset();
+        if (rv_status s = c->grec_stage.reserve(c, nstage * sizeof(uint2))) return s;
+        if (rv_status s = c->grec_all.reserve(c, nall * sizeof(uint2))) return s;
+        if (rv_status s = c->gring.reserve(c, cap * 4)) return s;
         // a record slot nobody wrote (other ranks' chunks under the timing probe) reads as a solid cell;
         // on S: a plain hipMemset runs on the legacy stream, which does not order with S
         HIP_TRY(c, hipMemsetAsync(c->grec_all, 0, nall * sizeof(uint2), S));
     }
-    for (hipEvent_t& e : c->gev)
-        if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hipEvent_t& ev_rendered = c->gev[0];
-    hipEvent_t& ev_applied = c->gev[1];
-    hipEvent_t& ev_allg = c->gev[2];
-    hipEvent_t* ev_pb = &c->gev[3];        // [2] phase B of group h done (slot h & 1)
-    hipEvent_t* ev_gath = &c->gev[5];      // [2] tile gather of group g done (slot g & 1)
-    hipEvent_t& ev_tmp = c->gev[7];
-    if (!c->grp_stream) HIP_TRY(c, hipStreamCreateWithPriority(&c->grp_stream, hipStreamNonBlocking, c->prio_hi));
+    for (Event& e : c->gev)
+        if (rv_status s = e.ensure(c)) return s;
+    const hipEvent_t ev_rendered = c->gev[0], ev_applied = c->gev[1], ev_allg = c->gev[2], ev_tmp = c->gev[7];
+    const Event* ev_pb = &c->gev[3];       // [2] phase B of group h done (slot h & 1)
+    const Event* ev_gath = &c->gev[5];     // [2] tile gather of group g done (slot g & 1)
+    if (rv_status s = c->grp_stream.ensure(c, c->prio_hi)) return s;
     hipStream_t SB = c->grp_stream;
-    slot_save(c);
     slot_load(c, 0);
     c->stream = S;
     if (rv_status ws = wait_all_frames(c)) return ws;   // frames of earlier calls, the last world write
@@ -532,7 +523,7 @@ static rv_status render_gi_group(rv_ctx* c, const Seq& q, int32_t flags, hipStre
         if (tiles) {
             f.tiles = c->tiles.d; f.ntiles = (int)c->shard_ids.size(); f.tile_px = T; f.tiles_x = tiles_x;
             f.tilebuf = bs.tbuf; f.tile_bpp = bpp; f.bs_tile = slice;
-            f.chunk_order[CG_RENDER] = c->tile_order; f.chunk_cost[CG_RENDER] = c->tile_cost;
+            f.chunk_order[CG_RENDER] = cur(c).tile_order; f.chunk_cost[CG_RENDER] = cur(c).tile_cost;
         }
         GroupParams gp{};
         gp.nr = g >= 0 ? (uint32_t)nfr(g) : 0u;
@@ -638,13 +629,14 @@ static rv_status render_gi_group(rv_ctx* c, const Seq& q, int32_t flags, hipStre
         HIP_TRY(c, hipEventRecord(ev_applied, S));
         FrameParams fo = make_params_d(c, q.at(g * F), flags);   // SCHED_COST re-order after every group
         if (fo.sched == SCHED_COST) {
+            const FrameSlot& sl = cur(c);
             if (tiles) {
                 const uint32_t nt = (uint32_t)c->shard_ids.size();
-                launch_chunk_order(S, c->tile_cost, c->tile_order, nt, (nt + 7u) & ~7u);
+                launch_chunk_order(S, sl.tile_cost, sl.tile_order, nt, (nt + 7u) & ~7u);
             } else {
-                launch_chunk_order(S, c->chunk_cost[CG_PREPASS], c->chunk_order[CG_PREPASS], n_chunks(fo.hw, fo.hh),
-                                   n_chunks_pad(fo.hw, fo.hh), c->chunk_cost[CG_RENDER],
-                                   c->chunk_order[CG_RENDER], n_chunks(W, H), n_chunks_pad(W, H));
+                launch_chunk_order(S, sl.chunk_cost[CG_PREPASS], sl.chunk_order[CG_PREPASS], n_chunks(fo.hw, fo.hh),
+                                   n_chunks_pad(fo.hw, fo.hh), sl.chunk_cost[CG_RENDER],
+                                   sl.chunk_order[CG_RENDER], n_chunks(W, H), n_chunks_pad(W, H));
             }
             LAUNCH_CHECK(c);
         }
@@ -659,7 +651,7 @@ static rv_status render_gi_group(rv_ctx* c, const Seq& q, int32_t flags, hipStre
             if (rv_status gs = comm_group_start(c, comm)) return gs;
             if (root) {
                 for (int r = 1; r < N; r++)
-                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(bs.gbuf) + (size_t)r * sb, sb, r,
+                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(bs.gbuf.p) + (size_t)r * sb, sb, r,
                                                  c->comm_stream))
                         return rs;
             } else {
@@ -732,14 +724,12 @@ static rv_status render_batches(rv_ctx* c, const Seq& q, int32_t flags, rv_comm*
     // alternates two streams so a group's tail overlaps the next group
     hipStream_t S[2] = {own0 ? c->fstreams[0] : caller, own0 ? c->fstreams[1] : c->fstreams[0]};
     if (c->batch_streams < 2) S[1] = S[0];
-    slot_save(c);
     if (tiles) {   // device tile lists and both slots' orders, on the caller's stream
         c->stream = caller;
         if (rv_status us = upload_ids(c, c->untile_ids, c->shard_all.data(), (int)c->shard_all.size(), nullptr)) return us;
         for (int k = 0; k < 2; k++) {
             slot_load(c, k);
             if (rv_status ts = tile_list(c, c->shard_ids.data(), (int32_t)c->shard_ids.size(), T)) return ts;
-            slot_save(c);
         }
     }
     HIP_TRY(c, hipEventRecord(c->ev_loop, caller));
@@ -770,7 +760,6 @@ static rv_status render_batches(rv_ctx* c, const Seq& q, int32_t flags, rv_comm*
         const int nb = (frames - done + groups - 1) / groups, k = j & 1;
         BatchSet& bs = c->bsets[k];
         c->stream = S[k];
-        slot_save(c);
         slot_load(c, k);
         if (bs.pending && tiles && !root) HIP_TRY(c, hipStreamWaitEvent(S[k], bs.gathered, 0));   // tile buffer reuse
         FrameParams f = make_params_d(c, q.at(done), flags);
@@ -785,7 +774,7 @@ static rv_status render_batches(rv_ctx* c, const Seq& q, int32_t flags, rv_comm*
             f.tiles = c->tiles.d; f.ntiles = (int)c->shard_ids.size(); f.tile_px = T;
             f.tiles_x = (W + T - 1) / T;
             f.tilebuf = bs.tbuf; f.bs_tile = slice; f.tile_bpp = bpp;
-            f.chunk_order[CG_RENDER] = c->tile_order; f.chunk_cost[CG_RENDER] = c->tile_cost;
+            f.chunk_order[CG_RENDER] = cur(c).tile_order; f.chunk_cost[CG_RENDER] = cur(c).tile_cost;
         }
         if (rv_status rs = run_stages(c, f, tiles)) return rs;
         c->frame_seq += (uint64_t)nb;
@@ -798,7 +787,7 @@ static rv_status render_batches(rv_ctx* c, const Seq& q, int32_t flags, rv_comm*
             if (rv_status gs = comm_group_start(c, comm)) return gs;
             if (root) {
                 for (int q = 1; q < c->shard_n; q++)
-                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(bs.gbuf) + (size_t)q * part, part, q, c->comm_stream)) return rs;
+                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(bs.gbuf.p) + (size_t)q * part, part, q, c->comm_stream)) return rs;
             } else {
                 if (rv_status ss = comm_send(c, comm, bs.tbuf, part, 0, c->comm_stream)) return ss;
             }
@@ -820,7 +809,6 @@ static rv_status render_batches(rv_ctx* c, const Seq& q, int32_t flags, rv_comm*
     if (prev_k >= 0)
         if (rv_status us = untile_group(prev_k, prev_nb)) return us;
     // the last frame becomes slot 0's images (rv_readback / rv_image_ptr)
-    slot_save(c);
     slot_load(c, 0);
     c->stream = S[last];
     if (!tiles || root)
@@ -918,10 +906,10 @@ static rv_status verify_ranks(rv_ctx* c, rv_comm* comm, int32_t flags, int32_t g
     // pipelined / GI groups / per frame) and the frame count shape the sequence of collectives too
     mix((uint64_t)loop); mix((uint64_t)gi_per_frame); mix((uint64_t)frames); mix((uint64_t)c->slots.size());
     for (int32_t t : c->shard_all) mix((uint64_t)(uint32_t)t);
-    if (!c->comm_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
+    if (rv_status s = c->comm_stream.ensure(c)) return s;
     const size_t nr = (size_t)comm->nranks;
-    if (!comm->vdev) HIP_TRY(c, hipMalloc(&comm->vdev, 8 * (nr + 1)));
-    if (!comm->vhost) HIP_TRY(c, hipHostMalloc(&comm->vhost, 8 * (nr + 1), hipHostMallocDefault));
+    if (rv_status s = comm->vdev.reserve(c, 8 * (nr + 1))) return s;
+    if (rv_status s = comm->vhost.reserve(c, 8 * (nr + 1))) return s;
     // the pinned word holding this rank's hash is read by the upload below before the bounded wait returns
     comm->vhost[nr] = h;
     rv_status st = RV_OK;
@@ -969,7 +957,6 @@ static rv_status render_seq(rv_ctx* c, const Seq& q, int32_t flags, int32_t gi_p
     if (!c->fstreams.empty() && c->fstream_prio != prio) {
         // only the streams depend on the priority; batch buffers and events stay
         HIP_TRY(c, hipDeviceSynchronize());
-        for (hipStream_t fs : c->fstreams) hipStreamDestroy(fs);
         c->fstreams.clear();
     }
     c->fstream_prio = prio;
@@ -978,23 +965,22 @@ static rv_status render_seq(rv_ctx* c, const Seq& q, int32_t flags, int32_t gi_p
     const bool own0 = c->stream == nullptr;
     const int nown = own0 ? n : n - 1;
     while ((int)c->fstreams.size() < nown) {
-        hipStream_t st;
-        HIP_TRY(c, hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio));
-        c->fstreams.push_back(st);
+        Stream st;
+        if (rv_status s = st.ensure(c, prio)) return s;
+        c->fstreams.push_back(std::move(st));
     }
-    if (!c->ev_loop) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_loop, hipEventDisableTiming));
+    if (rv_status s = c->ev_loop.ensure(c)) return s;
     if (tiles) {
-        if (comm && !c->comm_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
+        if (comm)
+            if (rv_status s = c->comm_stream.ensure(c)) return s;
         const bool root = c->shard_rank == 0;
         const size_t gneed = root ? slice * (size_t)c->shard_n : 0;
         for (FrameSlot& sl : c->slots) {
-            if (sl.tbytes != slice || sl.gbytes != gneed) {
+            if (sl.tbuf.cap != slice || sl.gbuf.cap != gneed) {
                 HIP_TRY(c, hipDeviceSynchronize());
-                hipFree(sl.tbuf); hipFree(sl.gbuf);
-                sl.tbuf = nullptr; sl.gbuf = nullptr; sl.tbytes = sl.gbytes = 0;
-                HIP_TRY(c, hipMalloc(&sl.tbuf, slice));
-                if (gneed) HIP_TRY(c, hipMalloc(&sl.gbuf, gneed));
-                sl.tbytes = slice; sl.gbytes = gneed;
+                sl.tbuf.reset(); sl.gbuf.reset();
+                if (rv_status s = sl.tbuf.reserve(c, slice)) return s;
+                if (rv_status s = sl.gbuf.reserve(c, gneed)) return s;   // rank 0 only
             }
         }
     }
@@ -1046,7 +1032,7 @@ static rv_status render_seq(rv_ctx* c, const Seq& q, int32_t flags, int32_t gi_p
         const rv_frame_desc& d = q.at(k);
         if (!tiles) { st = rv_frame(c, &d.cam, d.vp, d.prev_vp, d.time, d.jitter_x, d.jitter_y, flags); continue; }
         FrameSlot& sl = c->slots[s];
-        c->ext_tilebuf = sl.tbuf; c->ext_tilebuf_bytes = sl.tbytes;
+        c->ext_tilebuf = sl.tbuf; c->ext_tilebuf_bytes = sl.tbuf.cap;
         st = rv_frame_tiles(c, &d.cam, d.vp, d.prev_vp, d.time, d.jitter_x, d.jitter_y, flags, c->shard_ids.data(),
                             (int32_t)c->shard_ids.size(), T);
         if (st != RV_OK) break;
@@ -1059,7 +1045,7 @@ static rv_status render_seq(rv_ctx* c, const Seq& q, int32_t flags, int32_t gi_p
             if (rv_status gs = comm_group_start(c, comm)) return gs;
             if (c->shard_rank == 0) {
                 for (int q = 1; q < c->shard_n; q++)
-                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(sl.gbuf) + (size_t)q * slice, slice, q, c->comm_stream)) return rs;
+                    if (rv_status rs = comm_recv(c, comm, reinterpret_cast<char*>(sl.gbuf.p) + (size_t)q * slice, slice, q, c->comm_stream)) return rs;
             } else {
                 if (rv_status ss = comm_send(c, comm, sl.tbuf, slice, 0, c->comm_stream)) return ss;
             }

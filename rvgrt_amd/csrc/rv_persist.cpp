@@ -84,24 +84,14 @@ size_t persist_stored_in(const rv_ctx* c, const ColumnRange& r, int32_t ox, int3
 rv_status persist_reserve(rv_ctx* c, size_t ncols) {
     if (ncols == 0) return RV_OK;
     const size_t bytes = ncols * column_words(c) * 4;
-    if (rv_status s = dev_reserve(c, c->persist_cols, c->persist_cols_cap, ncols * sizeof(int2))) return s;
-    if (rv_status s = dev_reserve(c, c->persist_stage, c->persist_stage_cap, bytes)) return s;
-    if (bytes > c->persist_stage_h_cap) {
-        hipHostFree(c->persist_stage_h);
-        c->persist_stage_h = nullptr;
-        c->persist_stage_h_cap = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->persist_stage_h, bytes, hipHostMallocDefault));
-        c->persist_stage_h_cap = bytes;
-    }
-    return RV_OK;
+    if (rv_status s = c->persist_cols.reserve(c, ncols * sizeof(int2))) return s;
+    if (rv_status s = c->persist_stage.reserve(c, bytes)) return s;
+    return c->persist_stage_h.reserve(c, bytes);
 }
 
 void persist_trim(rv_ctx* c) {
-    if (c->persist_stage_cap <= EDIT_SCRATCH_KEEP) return;
-    hipFree(c->persist_stage);
-    hipHostFree(c->persist_stage_h);
-    c->persist_stage = c->persist_stage_h = nullptr;
-    c->persist_stage_cap = c->persist_stage_h_cap = 0;
+    c->persist_stage.trim(EDIT_SCRATCH_KEEP);
+    c->persist_stage_h.trim(EDIT_SCRATCH_KEEP);
 }
 
 rv_status persist_capture(rv_ctx* c, const ColumnRange& r, bool keep_dirty) {

@@ -49,18 +49,19 @@ rv_status rv_gi_relight(rv_ctx* c, const rv_gi_box* box, uint32_t frame0, int32_
     // dense array by the grid's own size.  An array that has to grow is freed only once the last relight, which
     // ended in mark_world, has finished with it.
     const size_t rec_need = (size_t)records * sizeof(uint2), dense_need = (size_t)cells * 4;
-    if (rec_need > c->relight_rec_cap || dense_need > c->relight_dense_cap[0] || dense_need > c->relight_dense_cap[1])
+    if (rec_need > c->relight_rec.cap || dense_need > c->relight_dense[0].cap || dense_need > c->relight_dense[1].cap)
         HIP_TRY(c, hipEventSynchronize(c->ev_world));
-    if (rv_status s = dev_reserve(c, c->relight_rec, c->relight_rec_cap, rec_need)) return s;
+    if (rv_status s = c->relight_rec.reserve(c, rec_need)) return s;
     for (int k = 0; k < 2; k++)
-        if (rv_status s = dev_reserve(c, c->relight_dense[k], c->relight_dense_cap[k], dense_need)) return s;
+        if (rv_status s = c->relight_dense[k].reserve(c, dense_need)) return s;
+    uint32_t* const dense[2] = {c->relight_dense[0], c->relight_dense[1]};
 
     // Ordered like rv_gi_update: after the frames in flight and the last world/GI write.  The call reads
     // and writes the grid and its own scratch only (never gi_tmp), on the context's stream.
     if (rv_status ws = wait_all_frames(c)) return ws;
     launch_gi_relight(c->stream, current_world(c), sun_dir(), b, frame0, (uint32_t)iterations, init,
                       c->cfg.gi_init_saturate ? RV_GI_LIT_SATURATE : RV_GI_LIT_REFERENCE, c->gi, c->relight_rec,
-                      c->relight_dense, c->counters + ST_GI * NCNT);
+                      dense, c->counters + ST_GI * NCNT);
     LAUNCH_CHECK(c);
     c->relight_calls++;
     c->relight_cells += cells;

@@ -91,7 +91,7 @@ rv_status scroll_axis(rv_ctx* c, int axis, int d, uint64_t* cells, int* full) {
     // the scratch copy of the retained brick records (128 B each; the GI cells' 32 B per brick reuse it),
     // before anything is written: a failed allocation leaves the world as it was
     const size_t kept = (size_t)(NB - ab) * (size_t)(axis == 0 ? NBZ : NBX) * (size_t)NBY;
-    if (rv_status s = dev_reserve(c, c->scroll_tmp, c->scroll_tmp_cap, kept * 128)) return s;
+    if (rv_status s = c->scroll_tmp.reserve(c, kept * 128)) return s;
     // persistence: the brick columns that leave (old window) and those that enter (new window), and the
     // staging for the dirty ones among the former and the stored ones among the latter, reserved here too
     ColumnRange col_leave{0, NBX, 0, NBZ}, col_enter = col_leave;
@@ -208,11 +208,7 @@ rv_status rv_world_scroll(rv_ctx* c, int32_t dx, int32_t dz) {
     if (dx != 0) s = scroll_axis(c, 0, dx, &cells, &full);
     if (s == RV_OK && dz != 0) s = scroll_axis(c, 2, dz, &cells, &full);
     const hipError_t se = hipStreamSynchronize(c->stream);
-    if (c->scroll_tmp_cap > EDIT_SCRATCH_KEEP) {
-        hipFree(c->scroll_tmp);
-        c->scroll_tmp = nullptr;
-        c->scroll_tmp_cap = 0;
-    }
+    c->scroll_tmp.trim(EDIT_SCRATCH_KEEP);
     persist_trim(c);
     if (s != RV_OK) return s;
     HIP_TRY(c, se);
@@ -272,22 +268,17 @@ rv_status rv_texture_tiles(rv_ctx* c, const float* pos, int64_t n, uint8_t* tile
     if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_texture_tiles before a world build or import");
     if (n == 0) return RV_OK;
     if (rv_status ws = wait_all_frames(c)) return ws;
-    float* dp = nullptr;
-    uint8_t* dt = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&dp, (size_t)n * 12));
-    if (hipMalloc((void**)&dt, (size_t)n) != hipSuccess) {
-        hipFree(dp);
-        return fail(c, RV_ERR_OOM, "rv_texture_tiles: out of device memory");
-    }
+    DevBuf<float> dp;
+    DevBuf<uint8_t> dt;
+    if (rv_status s = dp.reserve(c, (size_t)n * 12)) return s;
+    if (dt.reserve(c, (size_t)n)) return fail(c, RV_ERR_OOM, "rv_texture_tiles: out of device memory");
     hipError_t e = hipMemcpyAsync(dp, pos, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         launch_texture_tiles(c->stream, current_world(c), dp, n, dt);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(tiles, dt, (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);
-    hipFree(dp);
-    hipFree(dt);
+    const hipError_t se = hipStreamSynchronize(c->stream);   // before dp and dt go
     HIP_TRY(c, e);
     HIP_TRY(c, se);
     return RV_OK;
