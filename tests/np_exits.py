@@ -172,10 +172,13 @@ def _max_over_columns(ct, cost, valid):
     base = np.where(solid, ct.astype(np.float64), -np.inf)
     pen = np.where(valid, cost, np.inf)
     out = np.full((ncz, ncx), -np.inf)
-    for cz in range(ncz):
-        for cx in range(ncx):
-            w = pen[ncz - 1 - cz:2 * ncz - 1 - cz, ncx - 1 - cx:2 * ncx - 1 - cx]
-            out[cz, cx] = (base - w).max()
+    # offset by offset over the valid ones (a narrow band along the sun's direction): the same differences
+    # as column by column, and a max does not depend on the order of its arguments
+    for j, i in np.argwhere(np.isfinite(pen)):
+        dz, dx = int(j) - (ncz - 1), int(i) - (ncx - 1)      # b - c
+        c = (slice(max(0, -dz), min(ncz, ncz - dz)), slice(max(0, -dx), min(ncx, ncx - dx)))
+        b = (slice(max(0, dz), min(ncz, ncz + dz)), slice(max(0, dx), min(ncx, ncx + dx)))
+        np.maximum(out[c], base[b] - pen[j, i], out=out[c])
     return out
 
 
@@ -235,6 +238,7 @@ def horizon_f32(ct, sun, topmax):
     H = np.zeros(ncz * ncx, f)
     act = np.arange(ncz * ncx)                   # the columns still scanning
     sidx = int(np.floor(f(f(-2.0) * R) - f(0.5)))
+    o5z, o5x = (v.reshape(25, 1) for v in np.divmod(np.arange(25), 5))
     topmax = f(topmax)
     while act.size:
         t = f(sidx)
@@ -252,33 +256,41 @@ def horizon_f32(ct, sun, topmax):
         cur = act if t > 0 else act[~out]
         b0x = np.floor(((qx - f(4.4)).astype(f) * f(0.5)).astype(f)).astype(np.int64)
         b0z = np.floor(((qz - f(4.4)).astype(f) * f(0.5)).astype(f)).astype(np.int64)
-        for oz in range(5):
-            for ox in range(5):
-                bx, bz = b0x + ox, b0z + oz
-                ok = (bx >= 0) & (bz >= 0) & (bx < ncx) & (bz < ncz)
-                tp = np.where(ok, top[np.clip(bz, 0, ncz - 1) * ncx + np.clip(bx, 0, ncx - 1)], 0)
-                ok &= tp != 0
-                dx = ((f(2.0) * bx.astype(f) + f(1.0)).astype(f) - cx[cur]).astype(f)
-                dz = ((f(2.0) * bz.astype(f) + f(1.0)).astype(f) - cz[cur]).astype(f)
-                du = ((dx * ux).astype(f) + (dz * uz).astype(f)).astype(f)
-                dn = ((dx * nx).astype(f) + (dz * nz).astype(f)).astype(f)
-                ok &= ~((np.abs(dn) > f(R2 + f(0.01))) | (du < f(f(-2.0) * R - f(0.01))))
-                h = (du - R2).astype(f)
-                h = np.where(h > 0, h, f(0.0)).astype(f)
-                v = ((tp.astype(f) + f(2.0)).astype(f) - (k * h).astype(f)).astype(f)
-                H[cur] = np.where(ok & (v > H[cur]), v, H[cur])
+        # the 5 x 5 columns around the sample, all at once: [25, columns]
+        bx, bz = b0x[None, :] + o5x, b0z[None, :] + o5z
+        ok = (bx >= 0) & (bz >= 0) & (bx < ncx) & (bz < ncz)
+        tp = np.where(ok, top[np.clip(bz, 0, ncz - 1) * ncx + np.clip(bx, 0, ncx - 1)], 0)
+        ok &= tp != 0
+        dx = ((f(2.0) * bx.astype(f) + f(1.0)).astype(f) - cx[cur]).astype(f)
+        dz = ((f(2.0) * bz.astype(f) + f(1.0)).astype(f) - cz[cur]).astype(f)
+        du = ((dx * ux).astype(f) + (dz * uz).astype(f)).astype(f)
+        dn = ((dx * nx).astype(f) + (dz * nz).astype(f)).astype(f)
+        ok &= ~((np.abs(dn) > f(R2 + f(0.01))) | (du < f(f(-2.0) * R - f(0.01))))
+        h = (du - R2).astype(f)
+        h = np.where(h > 0, h, f(0.0)).astype(f)
+        v = ((tp.astype(f) + f(2.0)).astype(f) - (k * h).astype(f)).astype(f)
+        H[cur] = np.maximum(H[cur], np.where(ok, v, f(0.0)).max(axis=0))   # H >= 0: a column that is not ok adds 0
     return np.ceil(H).astype(np.uint32).reshape(ncz, ncx)
 
 
 _REF = {}
+_HORIZON = {}
+
+
+def _horizons(ct, sun, yt):
+    """The three horizon statements, which read the column tops alone: once per set of tops."""
+    key = (ct.shape, ct.tobytes(), np.asarray(sun, np.float32).tobytes(), yt)
+    if key not in _HORIZON:
+        _HORIZON[key] = {"safety": horizon_safety(ct, sun), "tightness": horizon_tightness(ct, sun),
+                         "f32": horizon_f32(ct, sun, yt)}
+    return _HORIZON[key]
 
 
 def reference(vox, sun, key=None):
     """Every table's reference for these voxels, computed once per key (a world's name; None: not kept)."""
     if key is None or key not in _REF:
         ct, yt = coltop(vox), ytop(vox)
-        ref = {"ytop": yt, "coltop": ct, "dtop": dtop(vox), "safety": horizon_safety(ct, sun),
-               "tightness": horizon_tightness(ct, sun), "f32": horizon_f32(ct, sun, yt)}
+        ref = {"ytop": yt, "coltop": ct, "dtop": dtop(vox), **_horizons(ct, sun, yt)}
         if key is None:
             return ref
         _REF[key] = ref

@@ -177,3 +177,22 @@ def test_the_pillar_stands_in_the_skimming_rays_path(oracle, sun):
     shadowed = int((a["hit"] != b["hit"]).sum())
     print(f"pillar: {changed} column rays and {shadowed} sun rays change their result")
     assert changed >= 10 and shadowed >= 10
+
+
+def test_max_over_columns_equals_the_column_by_column_loop():
+    """np_exits._max_over_columns walks the valid offsets; the plain statement walks the columns."""
+    rng = np.random.default_rng(3)
+    for ncz, ncx in ((5, 9), (16, 4), (1, 7), (12, 12)):
+        ct = rng.integers(0, 40, (ncz, ncx)).astype(np.uint32)
+        ct[rng.uniform(size=ct.shape) < 0.3] = 0                       # empty columns
+        for density in (0.0, 0.05, 0.5, 1.0):
+            valid = rng.uniform(size=(2 * ncz - 1, 2 * ncx - 1)) < density
+            cost = rng.normal(0, 20, valid.shape)
+            cost[~valid & (rng.uniform(size=valid.shape) < 0.5)] = np.inf   # as the safety bound leaves them
+            base = np.where(ct > 0, ct.astype(np.float64), -np.inf)
+            pen = np.where(valid, cost, np.inf)
+            want = np.full((ncz, ncx), -np.inf)
+            for cz in range(ncz):
+                for cx in range(ncx):
+                    want[cz, cx] = (base - pen[ncz - 1 - cz:2 * ncz - 1 - cz, ncx - 1 - cx:2 * ncx - 1 - cx]).max()
+            assert np.array_equal(E._max_over_columns(ct, cost, valid), want), (ncz, ncx, density)
