@@ -82,6 +82,13 @@ public:
     // Place / break blocks (no reference counterpart: its world is fixed after CArray::fill): voxel
     // boxes set or cleared in place, the CSDF and the early exits rebuilt around them (rv_world_edit)
     void editWorld(const rv_edit_box* boxes, int n) { check(rv_world_edit(ctx_, boxes, n), ctx_, "rv_world_edit"); }
+    // What an edit left floating in a voxel box: up to cap components into comps, their total returned; with
+    // RV_DETACHED_CLEAR they are cleared like an editWorld of those voxels (rv_world_detached)
+    int64_t findDetached(const rv_voxel_box& box, int flags, rv_component* comps, int64_t cap, uint64_t* voxels = nullptr) {
+        int64_t n = 0;
+        check(rv_world_detached(ctx_, &box, flags, comps, cap, &n, voxels, nullptr, 0), ctx_, "rv_world_detached");
+        return n;
+    }
     // The world window moved by (dx, 0, dz) voxels over the generated terrain, in place (rv_world_scroll)
     void scroll(int dx, int dz) { check(rv_world_scroll(ctx_, dx, dz), ctx_, "rv_world_scroll"); }
     // The texture origin (rv_texture_origin_set) and whether scroll() moves it with the window

@@ -92,6 +92,20 @@ RV_BODY_START_SOLID, RV_BODY_EDGE, RV_BODY_INVALID = 64, 128, 256
 RV_BODIES_OPEN_EDGES = 1
 RV_BODIES_MAX = 1 << 24
 
+
+class rv_voxel_box(C.Structure):
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32),
+                ("x1", C.c_int32), ("y1", C.c_int32), ("z1", C.c_int32)]
+
+
+class rv_component(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("seed", C.c_int32 * 3), ("voxels", C.c_uint32)]
+
+
+# rv_world_detached's flags and the cap on a box's volume
+RV_DETACHED_CLEAR = 1
+RV_DETACHED_MAX_VOXELS = 1 << 21
+
 STAT_FIELDS = ["traces", "primary", "shadow", "refl", "refl_shadow", "prepass_primary",
                "prepass_shadow", "cones", "cone_steps", "sphere_steps", "dda_steps",
                "csdf_checks", "tex_samples", "undef_hits", "gi_traces", "frames"]
@@ -160,6 +174,10 @@ SIGNATURES = [
     ("rv_world_bodies_move_device", I32, [P, P, I64, I32, P]),
     ("rv_world_bodies_move_at", I32, [I32, I32, I32, P, P, I64, I32, P]),
     ("rv_world_bodies_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rv_world_detached", I32, [P, C.POINTER(rv_voxel_box), I32, P, I64, C.POINTER(I64), C.POINTER(U64), P, SZ]),
+    ("rv_world_detached_at", I32, [I32, I32, I32, P, C.POINTER(rv_voxel_box), P, I64, C.POINTER(I64),
+                                   C.POINTER(U64), P, SZ]),
+    ("rv_world_detached_info", I32, [P, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]),
     ("rv_texture_origin_set", I32, [P, I32, I32]),
     ("rv_texture_follow_scroll", I32, [P, I32]),
     ("rv_texture_origin_get", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

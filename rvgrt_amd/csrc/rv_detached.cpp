@@ -1,0 +1,169 @@
+// rv_detached.cpp -- host side of librvgrt_hip.so, part 9 of the C ABI (include/rvgrt.h): the voxels of a box
+// that nothing holds any more, found and optionally cleared (rv_world_detached, rv_world_detached_info), and
+// the host-only evaluation of the same query (rv_world_detached_at).  The per-word functions are in
+// include/rvgrt/rv_detached.h, the kernels in rv_detached.hip.  The query reads the bits and writes nothing
+// the frames read; the clear ends like an rv_world_edit of the same voxels (edit_finish, rv_edit.cpp).
+#include "rv_host.h"
+#include "../../include/rvgrt/rv_detached.h"
+
+static_assert(sizeof(rv_component) == 40 && sizeof(rv_voxel_box) == 24, "rv_component / rv_voxel_box layout");
+
+namespace {
+
+bool args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const rv_component* comps, int64_t cap,
+             const uint32_t* mask, size_t mask_bytes) {
+    if (!b || (flags & ~RV_DETACHED_CLEAR) || cap < 0 || (cap > 0 && !comps)) return false;
+    if (b->x0 < 0 || b->y0 < 0 || b->z0 < 0 || b->x1 > X || b->y1 > Y || b->z1 > Z) return false;
+    if (b->x1 <= b->x0 || b->y1 <= b->y0 || b->z1 <= b->z0) return false;
+    const uint64_t V = (uint64_t)(b->x1 - b->x0) * (uint64_t)(b->y1 - b->y0) * (uint64_t)(b->z1 - b->z0);
+    if (V > RV_DETACHED_MAX_VOXELS) return false;
+    return !mask || mask_bytes >= 4 * ((V + 31) / 32);
+}
+
+// The nc records (DETACH_REC dwords each, box-local) in ascending order of their seeds, as rv_component in
+// window coordinates: the first min(cap, nc) of them.
+void write_components(const DetachBox& b, uint32_t* rec, uint32_t nc, rv_component* comps, int64_t cap) {
+    std::vector<uint32_t> order(nc);
+    for (uint32_t i = 0; i < nc; i++) order[i] = i;
+    std::sort(order.begin(), order.end(),
+              [&](uint32_t p, uint32_t q) { return rec[DETACH_REC * p + 7] < rec[DETACH_REC * q + 7]; });
+    const int o[3] = {b.x0, b.y0, b.z0};
+    for (int64_t i = 0; i < std::min<int64_t>(cap, nc); i++) {
+        const uint32_t* r = rec + (size_t)DETACH_REC * order[i];
+        rv_component& k = comps[i];
+        for (int a = 0; a < 3; a++) {
+            k.lo[a] = o[a] + (int32_t)r[1 + a];
+            k.hi[a] = o[a] + (int32_t)r[4 + a] + 1;
+        }
+        const uint32_t n = r[7];
+        k.seed[0] = b.x0 + (int32_t)(n % (uint32_t)b.nx);
+        k.seed[1] = b.y0 + (int32_t)(n / (uint32_t)b.nx % (uint32_t)b.ny);
+        k.seed[2] = b.z0 + (int32_t)(n / (uint32_t)b.nx / (uint32_t)b.ny);
+        k.voxels = r[0];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+rv_status rv_world_detached(rv_ctx* c, const rv_voxel_box* box, int32_t flags, rv_component* comps, int64_t cap,
+                            int64_t* n_comps, uint64_t* n_voxels, uint32_t* mask, size_t mask_bytes) {
+    if (!c) return RV_ERR_INVALID;
+    if (!args_ok(1 << c->lx, 1 << c->ly, 1 << c->lz, box, flags, comps, cap, mask, mask_bytes))
+        return fail(c, RV_ERR_INVALID, "rv_world_detached: bad box, flags, cap or array");
+    if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_world_detached before a world build or import");
+    const DetachBox b = detach_box(*box);
+    const DetachLayout l = detach_layout(b);
+    const uint32_t V = b.voxels();
+    if (rv_status s = c->detach_scratch.reserve(c, l.total * 4)) return s;
+    // the last world write may have been issued on another stream
+    if (c->world_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_world, 0));
+    launch_detach_query(c->stream, current_world(c), b, c->detach_scratch);
+    LAUNCH_CHECK(c);
+    uint32_t cnt[2] = {0, 0};   // components, detached voxels
+    HIP_TRY(c, hipMemcpyAsync(cnt, c->detach_scratch + l.cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint32_t nc = cnt[0];
+    c->detach_h.resize((size_t)DETACH_REC * nc);
+    if (nc)
+        HIP_TRY(c, hipMemcpyAsync(c->detach_h.data(), c->detach_scratch + l.rec, (size_t)DETACH_REC * nc * 4,
+                                  hipMemcpyDeviceToHost, c->stream));
+    if (mask)
+        HIP_TRY(c, hipMemcpyAsync(mask, c->detach_scratch + l.mask, (size_t)((V + 31) / 32) * 4, hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t* rec = c->detach_h.data();
+    write_components(b, rec, nc, comps, cap);
+    if (n_comps) *n_comps = nc;
+    if (n_voxels) *n_voxels = cnt[1];
+    c->detach_calls++;
+    c->detach_scanned += V;
+
+    rv_status st = RV_OK;
+    if ((flags & RV_DETACHED_CLEAR) && cnt[1]) {
+        // the voxel box of everything detached, and the columns under each component for persistence
+        int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {0, 0, 0};
+        const int o[3] = {b.x0, b.y0, b.z0};
+        for (uint32_t i = 0; i < nc; i++)
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::min(lo[a], o[a] + (int)rec[DETACH_REC * i + 1 + a]);
+                hi[a] = std::max(hi[a], o[a] + (int)rec[DETACH_REC * i + 4 + a] + 1);
+            }
+        if (rv_status ws = wait_all_frames(c)) return ws;
+        launch_detach_clear(c->stream, c->brick, current_world(c), b, c->detach_scratch + l.D, lo, hi);
+        LAUNCH_CHECK(c);
+        for (uint32_t i = 0; i < nc; i++) {
+            const uint32_t* r = rec + (size_t)DETACH_REC * i;
+            persist_mark(c, ColumnRange{(b.x0 + (int)r[1]) >> 3, ((b.x0 + (int)r[4]) >> 3) + 1, (b.z0 + (int)r[3]) >> 3,
+                                        ((b.z0 + (int)r[6]) >> 3) + 1});
+        }
+        c->detach_cleared += cnt[1];
+        st = edit_finish(c, lo, hi);   // waits for the clear as well
+    }
+    c->detach_scratch.trim(EDIT_SCRATCH_KEEP);
+    return st;
+}
+
+rv_status rv_world_detached_info(rv_ctx* c, uint64_t* calls, uint64_t* voxels_scanned, uint64_t* voxels_cleared) {
+    if (!c) return RV_ERR_INVALID;
+    if (calls) *calls = c->detach_calls;
+    if (voxels_scanned) *voxels_scanned = c->detach_scanned;
+    if (voxels_cleared) *voxels_cleared = c->detach_cleared;
+    return RV_OK;
+}
+
+rv_status rv_world_detached_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, const uint32_t* bits,
+                               const rv_voxel_box* box, rv_component* comps, int64_t cap, int64_t* n_comps,
+                               uint64_t* n_voxels, uint32_t* mask, size_t mask_bytes) {
+    if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !bits) return RV_ERR_INVALID;
+    if (!args_ok(1 << log2_x, 1 << log2_y, 1 << log2_z, box, 0, comps, cap, mask, mask_bytes)) return RV_ERR_INVALID;
+    const LinearWorld w = linear_world(log2_x, log2_y, log2_z, bits, nullptr);
+    const DetachBox b = detach_box(*box);
+    const uint32_t V = b.voxels(), NW = b.words();
+    // the kernels' passes, word after word
+    std::vector<uint32_t> W(NW), L((size_t)V + 1), slot(V), rec;
+    for (uint32_t g = 0; g < NW; g++) W[g] = detach_gather_word(w, b, g);
+    L[0] = 0;
+    for (uint32_t g = 0; g < NW; g++) detach_init_word(L.data(), detach_word(b, g), W[g]);
+    for (uint32_t g = 0; g < NW; g++) detach_merge_word(w, b, W.data(), L.data(), g);
+    if (mask) std::memset(mask, 0, (size_t)((V + 31) / 32) * 4);
+    uint64_t nv = 0;
+    for (int pass = 0; pass < 2; pass++)   // flatten (roots take their slots), then stats
+        for (uint32_t g = 0; g < NW; g++) {
+            const DetachWord d = detach_word(b, g);
+            uint32_t m = W[g], s, len;
+            while (detach_next_run(m, s, len)) {
+                const uint32_t p = d.base + s;
+                if (pass == 0) {
+                    const uint32_t r = detach_find(L.data(), p);
+                    for (uint32_t k = 0; k < len; k++) L[p + k] = r;
+                    if (r == p) {
+                        slot[p - 1] = (uint32_t)(rec.size() / DETACH_REC);
+                        const uint32_t init[DETACH_REC] = {0, ~0u, ~0u, ~0u, 0, 0, 0, p - 1};
+                        rec.insert(rec.end(), init, init + DETACH_REC);
+                    }
+                    continue;
+                }
+                const uint32_t r = L[p];
+                if (r == 0) continue;
+                nv += len;
+                if (mask)
+                    for (uint32_t k = 0; k < len; k++) mask[(p - 1 + k) >> 5] |= 1u << ((p - 1 + k) & 31u);
+                uint32_t* q = rec.data() + (size_t)DETACH_REC * slot[r - 1];
+                const uint32_t lo[3] = {32u * (uint32_t)d.wx + s, (uint32_t)d.yl, (uint32_t)d.zl};
+                q[0] += len;
+                for (int a = 0; a < 3; a++) {
+                    q[1 + a] = std::min(q[1 + a], lo[a]);
+                    q[4 + a] = std::max(q[4 + a], a == 0 ? lo[0] + len - 1 : lo[a]);
+                }
+            }
+        }
+    const uint32_t nc = (uint32_t)(rec.size() / DETACH_REC);
+    write_components(b, rec.data(), nc, comps, cap);
+    if (n_comps) *n_comps = nc;
+    if (n_voxels) *n_voxels = nv;
+    return RV_OK;
+}
+
+}  // extern "C"

@@ -84,14 +84,10 @@ struct EditPlan {
     uint64_t full_cells;     // cells the four whole-grid passes visit
 };
 
-// boxes validated, n >= 1
-EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
+// the plan of an edit whose voxels lie in [lo, hi)
+EditPlan edit_plan_box(int lx, int ly, int lz, const int lo[3], const int hi[3]) {
     EditPlan p{};
-    for (int a = 0; a < 3; a++) { p.lo[a] = INT32_MAX; p.hi[a] = 0; }
-    for (int i = 0; i < n; i++) {
-        const int l[3] = {b[i].x0, b[i].y0, b[i].z0}, h[3] = {b[i].x1, b[i].y1, b[i].z1};
-        for (int a = 0; a < 3; a++) { p.lo[a] = std::min(p.lo[a], l[a]); p.hi[a] = std::max(p.hi[a], h[a]); }
-    }
+    for (int a = 0; a < 3; a++) { p.lo[a] = lo[a]; p.hi[a] = hi[a]; }
     const int S[3] = {1 << (lx - 1), 1 << (ly - 1), 1 << (lz - 1)};
     int e0[3], e1[3];
     for (int a = 0; a < 3; a++) { e0[a] = p.lo[a] >> 1; e1[a] = ((p.hi[a] - 1) >> 1) + 1; }
@@ -101,7 +97,40 @@ EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
     return p;
 }
 
+// boxes validated, n >= 1
+EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
+    int lo[3], hi[3];
+    for (int a = 0; a < 3; a++) { lo[a] = INT32_MAX; hi[a] = 0; }
+    for (int i = 0; i < n; i++) {
+        const int l[3] = {b[i].x0, b[i].y0, b[i].z0}, h[3] = {b[i].x1, b[i].y1, b[i].z1};
+        for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], l[a]); hi[a] = std::max(hi[a], h[a]); }
+    }
+    return edit_plan_box(lx, ly, lz, lo, hi);
+}
+
 }  // namespace
+
+// What follows the bit writes of an edit whose changed voxels lie in [lo, hi) (the caller has waited for the
+// frames, written the bits and marked the columns for persistence): shared by rv_world_edit and
+// rv_world_detached's clear.
+rv_status edit_finish(rv_ctx* c, const int lo[3], const int hi[3]) {
+    const EditPlan p = edit_plan_box(c->lx, c->ly, c->lz, lo, hi);
+    c->edit_cells = 0;
+    c->edit_full = 0;
+    c->geom_ver++;
+    if (rv_status ts = world_top(c)) return ts;   // the exits, from the bits (a cleared voxel can lower them)
+    if (p.local_cells >= p.full_cells) {
+        if (rv_status s = rv_csdf_build(c)) return s;
+        c->edit_cells = n_csdf(c);
+        c->edit_full = 1;
+    } else {
+        if (rv_status s = csdf_rebuild_boxes(c, &p.b, 1)) return s;
+        if (rv_status ms = mark_world(c)) return ms;
+        c->edit_cells = p.b.rf.cells();
+    }
+    c->edit_count++;
+    return RV_OK;
+}
 
 extern "C" {
 
@@ -149,19 +178,7 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
     for (int i = 0; i < n; i++)   // persistence: the columns under each box may now differ from the generator's
         persist_mark(c, ColumnRange{boxes[i].x0 >> 3, ((boxes[i].x1 - 1) >> 3) + 1, boxes[i].z0 >> 3,
                                     ((boxes[i].z1 - 1) >> 3) + 1});
-    c->geom_ver++;
-    if (rv_status ts = world_top(c)) return ts;   // the exits, from the bits (a cleared voxel can lower them)
-    if (p.local_cells >= p.full_cells) {
-        if (rv_status s = rv_csdf_build(c)) return s;
-        c->edit_cells = n_csdf(c);
-        c->edit_full = 1;
-    } else {
-        if (rv_status s = csdf_rebuild_boxes(c, &p.b, 1)) return s;
-        if (rv_status ms = mark_world(c)) return ms;
-        c->edit_cells = p.b.rf.cells();
-    }
-    c->edit_count++;
-    return RV_OK;
+    return edit_finish(c, p.lo, p.hi);
 }
 
 rv_status rv_world_edit_info(rv_ctx* c, uint64_t* edits, uint64_t* csdf_cells, int32_t* last_full) {

@@ -8,7 +8,8 @@
 //   rv_relight.cpp  the GI refresh of a cell box (rv_gi_relight);
 //   rv_scroll.cpp   the world window moved over the terrain (rv_world_scroll);
 //   rv_persist.cpp  edited columns kept across scrolls (rv_world_persist);
-//   rv_bodies.cpp   swept box collision against the voxel window (rv_world_bodies_move).
+//   rv_bodies.cpp   swept box collision against the voxel window (rv_world_bodies_move);
+//   rv_detached.cpp voxels an edit left floating, found and cleared (rv_world_detached).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -344,6 +345,12 @@ struct rv_ctx {
     // and rv_world_bodies_info's sums
     DevBuf<void> bodies_in, bodies_out;
     uint64_t bodies_calls = 0, bodies_moved = 0;
+    // rv_world_detached (rv_detached.cpp): the query's device scratch (one allocation laid out by
+    // detach_layout, freed after a call when above the edit scratch's keep limit), the host copy of the
+    // component records and rv_world_detached_info's sums
+    DevBuf<uint32_t> detach_scratch;
+    std::vector<uint32_t> detach_h;
+    uint64_t detach_calls = 0, detach_scanned = 0, detach_cleared = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;
@@ -546,6 +553,10 @@ constexpr size_t EDIT_SCRATCH_KEEP = (size_t)64 << 20;
 // the passes over `n` sets of boxes, one after the other, through edit_t0 / edit_t1; waits for them, then
 // frees the scratch when it is above EDIT_SCRATCH_KEEP
 RV_HIDDEN rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n);
+// The end of an edit whose changed voxels lie in the voxel box [lo, hi), after the caller has waited for the
+// frames, written the bits and marked the columns: geom_ver, the exits (world_top), the local CSDF rebuild
+// and mark_world or the whole-grid build, whichever visits fewer cells, and rv_world_edit_info's record
+RV_HIDDEN rv_status edit_finish(rv_ctx* c, const int lo[3], const int hi[3]);
 
 // rv_persist.cpp: the marking, capturing and restoring that rv_world_edit, rv_world_import, rv_world_build
 // and rv_world_scroll do while persistence is on (every one returns at once while it is off).  A range is

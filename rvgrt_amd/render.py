@@ -14,7 +14,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import RvError, rv_camera, rv_config, rv_edit_box, rv_frame_desc, rv_gi_box, rv_hit, rv_stats
+from ._lib import (RvError, rv_camera, rv_config, rv_edit_box, rv_frame_desc, rv_gi_box, rv_hit, rv_stats,
+                   rv_voxel_box)
 
 
 def _ptr(a: np.ndarray):
@@ -179,6 +180,43 @@ def bodies_move_at(log2_dims, bits, lo, size, delta, flags=0):
     if st != 0:
         raise RvError(f"rv_world_bodies_move_at: {_lib.STATUS_NAMES.get(st, st)}")
     return _bodies_out(out)
+
+
+# an array of rv_component
+COMPONENT_DTYPE = np.dtype([("lo", np.int32, 3), ("hi", np.int32, 3), ("seed", np.int32, 3), ("voxels", np.uint32)])
+
+
+def _voxel_box(box):
+    if len(box) != 6:
+        raise ValueError("a voxel box is (x0, y0, z0, x1, y1, z1)")
+    return rv_voxel_box(*(int(v) for v in box))
+
+
+def _box_volume(b):
+    return max(b.x1 - b.x0, 0) * max(b.y1 - b.y0, 0) * max(b.z1 - b.z0, 0)
+
+
+def detached_at(log2_dims, bits, box, cap=None, want_mask=True):
+    """rv_world_detached_at (host only): the query of StateRender.world_detached evaluated on the
+    CPU over `bits` (RV_WORLD_BITS layout, log2_x >= 5) by the functions the kernels call.  Returns
+    (components, n_comps, n_voxels, mask) like it; cap None = every component."""
+    L = _lib.load()
+    bits = np.ascontiguousarray(bits, np.uint32)
+    if bits.size != (1 << sum(int(v) for v in log2_dims)) // 32:
+        raise ValueError("bits does not match log2_dims")
+    b = _voxel_box(box)
+    lg = [int(v) for v in log2_dims]
+    if cap is None:
+        cap = (_box_volume(b) + 1) // 2
+    comps = np.zeros(max(int(cap), 1), COMPONENT_DTYPE)
+    mask = np.zeros(max((_box_volume(b) + 31) // 32, 1), np.uint32) if want_mask else None
+    n, v = C.c_int64(), C.c_uint64()
+    st = L.rv_world_detached_at(lg[0], lg[1], lg[2], _ptr(bits), C.byref(b), _ptr(comps) if cap else None, int(cap),
+                                C.byref(n), C.byref(v), None if mask is None else _ptr(mask),
+                                0 if mask is None else mask.nbytes)
+    if st != 0:
+        raise RvError(f"rv_world_detached_at: {_lib.STATUS_NAMES.get(st, st)}")
+    return comps[:min(int(cap), int(n.value))].copy(), int(n.value), int(v.value), mask
 
 
 def rccl_path():
@@ -555,6 +593,37 @@ class StateRender:
         n, b = C.c_uint64(), C.c_uint64()
         self._check(self._L.rv_world_bodies_info(self._h, C.byref(n), C.byref(b)), "rv_world_bodies_info")
         return int(n.value), int(b.value)
+
+    def world_detached(self, box, flags=0, cap=None, want_mask=True):
+        """rv_world_detached: the solid voxels of the voxel box (x0, y0, z0, x1, y1, z1) that nothing
+        holds -- no 6-connected path inside the box to solid matter beyond it, the floor or the window's
+        walls.  Returns (components, n_comps, n_voxels, mask): the first min(cap, n_comps) components
+        (COMPONENT_DTYPE: lo, hi, seed, voxels; cap None = all of them, by a counting call first), their
+        total, the detached voxels, and the mask words (None unless want_mask).
+        flags=RV_DETACHED_CLEAR clears them like a world_edit of those voxels; the results are those of
+        before the clear.  Synchronous."""
+        b = _voxel_box(box)
+        nw = (_box_volume(b) + 31) // 32
+        n, v = C.c_int64(), C.c_uint64()
+        if cap is None and not flags:
+            self._check(self._L.rv_world_detached(self._h, C.byref(b), 0, None, 0, C.byref(n), None, None, 0),
+                        "rv_world_detached")
+            cap = int(n.value)
+        elif cap is None:   # a clearing call runs once: room for the most a box can hold
+            cap = (_box_volume(b) + 1) // 2
+        comps = np.zeros(max(int(cap), 1), COMPONENT_DTYPE)
+        mask = np.zeros(max(nw, 1), np.uint32) if want_mask else None
+        self._check(self._L.rv_world_detached(self._h, C.byref(b), int(flags), _ptr(comps) if cap else None, int(cap),
+                                              C.byref(n), C.byref(v), None if mask is None else _ptr(mask),
+                                              0 if mask is None else mask.nbytes), "rv_world_detached")
+        return comps[:min(int(cap), int(n.value))].copy(), int(n.value), int(v.value), mask
+
+    def world_detached_info(self):
+        """(calls, voxels_scanned, voxels_cleared): sums over the world_detached calls that ran."""
+        n, s, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.rv_world_detached_info(self._h, C.byref(n), C.byref(s), C.byref(k)),
+                    "rv_world_detached_info")
+        return int(n.value), int(s.value), int(k.value)
 
     def gi_relight(self, box, frame0, iterations, init=False):
         """rv_gi_relight: `iterations` update steps (RNG frames frame0, frame0 + 1, ...)
