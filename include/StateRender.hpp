@@ -89,6 +89,14 @@ public:
         check(rv_world_detached(ctx_, &box, flags, comps, cap, &n, voxels, nullptr, 0), ctx_, "rv_world_detached");
         return n;
     }
+    // One round of falling: every detached component of the box drops until something stops it, or maxFall rows
+    // (0: no limit); up to cap records into comps, their total returned, the changed voxel box into *changed.
+    // Repeat over *changed until it returns 0 (rv_world_fall)
+    int64_t fallDetached(const rv_voxel_box& box, int maxFall, rv_fallen* comps, int64_t cap, rv_voxel_box* changed = nullptr) {
+        int64_t n = 0;
+        check(rv_world_fall(ctx_, &box, maxFall, comps, cap, &n, nullptr, changed), ctx_, "rv_world_fall");
+        return n;
+    }
     // The world window moved by (dx, 0, dz) voxels over the generated terrain, in place (rv_world_scroll)
     void scroll(int dx, int dz) { check(rv_world_scroll(ctx_, dx, dz), ctx_, "rv_world_scroll"); }
     // The texture origin (rv_texture_origin_set) and whether scroll() moves it with the window

@@ -106,6 +106,14 @@ class rv_component(C.Structure):
 RV_DETACHED_CLEAR = 1
 RV_DETACHED_MAX_VOXELS = 1 << 21
 
+
+class rv_fallen(C.Structure):
+    _fields_ = [("comp", rv_component), ("fall", C.c_int32), ("flags", C.c_uint32)]
+
+
+# rv_fallen.flags
+RV_FALL_STOPPED = 1
+
 STAT_FIELDS = ["traces", "primary", "shadow", "refl", "refl_shadow", "prepass_primary",
                "prepass_shadow", "cones", "cone_steps", "sphere_steps", "dda_steps",
                "csdf_checks", "tex_samples", "undef_hits", "gi_traces", "frames"]
@@ -178,6 +186,11 @@ SIGNATURES = [
     ("rv_world_detached_at", I32, [I32, I32, I32, P, C.POINTER(rv_voxel_box), P, I64, C.POINTER(I64),
                                    C.POINTER(U64), P, SZ]),
     ("rv_world_detached_info", I32, [P, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]),
+    ("rv_world_fall", I32, [P, C.POINTER(rv_voxel_box), I32, P, I64, C.POINTER(I64), C.POINTER(U64),
+                            C.POINTER(rv_voxel_box)]),
+    ("rv_world_fall_at", I32, [I32, I32, I32, P, C.POINTER(rv_voxel_box), I32, P, I64, C.POINTER(I64),
+                               C.POINTER(U64), C.POINTER(rv_voxel_box), P, SZ]),
+    ("rv_world_fall_info", I32, [P, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]),
     ("rv_texture_origin_set", I32, [P, I32, I32]),
     ("rv_texture_follow_scroll", I32, [P, I32]),
     ("rv_texture_origin_get", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -8,10 +8,10 @@
 
 static_assert(sizeof(rv_component) == 40 && sizeof(rv_voxel_box) == 24, "rv_component / rv_voxel_box layout");
 
-namespace {
-
-bool args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const rv_component* comps, int64_t cap,
-             const uint32_t* mask, size_t mask_bytes) {
+// shared with rv_fall.cpp (declared in rv_host.h): the argument check, the records' order and conversion, and
+// the host form of the query
+bool detach_args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const void* comps, int64_t cap,
+                    const uint32_t* mask, size_t mask_bytes) {
     if (!b || (flags & ~RV_DETACHED_CLEAR) || cap < 0 || (cap > 0 && !comps)) return false;
     if (b->x0 < 0 || b->y0 < 0 || b->z0 < 0 || b->x1 > X || b->y1 > Y || b->z1 > Z) return false;
     if (b->x1 <= b->x0 || b->y1 <= b->y0 || b->z1 <= b->z0) return false;
@@ -20,27 +20,82 @@ bool args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const rv
     return !mask || mask_bytes >= 4 * ((V + 31) / 32);
 }
 
-// The nc records (DETACH_REC dwords each, box-local) in ascending order of their seeds, as rv_component in
-// window coordinates: the first min(cap, nc) of them.
-void write_components(const DetachBox& b, uint32_t* rec, uint32_t nc, rv_component* comps, int64_t cap) {
+// the slots of nc records (DETACH_REC dwords each) in ascending order of their seeds
+std::vector<uint32_t> detach_seed_order(const uint32_t* rec, uint32_t nc) {
     std::vector<uint32_t> order(nc);
     for (uint32_t i = 0; i < nc; i++) order[i] = i;
     std::sort(order.begin(), order.end(),
               [&](uint32_t p, uint32_t q) { return rec[DETACH_REC * p + 7] < rec[DETACH_REC * q + 7]; });
+    return order;
+}
+
+// one box-local record as rv_component in window coordinates
+rv_component detach_component(const DetachBox& b, const uint32_t* r) {
+    rv_component k;
     const int o[3] = {b.x0, b.y0, b.z0};
-    for (int64_t i = 0; i < std::min<int64_t>(cap, nc); i++) {
-        const uint32_t* r = rec + (size_t)DETACH_REC * order[i];
-        rv_component& k = comps[i];
-        for (int a = 0; a < 3; a++) {
-            k.lo[a] = o[a] + (int32_t)r[1 + a];
-            k.hi[a] = o[a] + (int32_t)r[4 + a] + 1;
-        }
-        const uint32_t n = r[7];
-        k.seed[0] = b.x0 + (int32_t)(n % (uint32_t)b.nx);
-        k.seed[1] = b.y0 + (int32_t)(n / (uint32_t)b.nx % (uint32_t)b.ny);
-        k.seed[2] = b.z0 + (int32_t)(n / (uint32_t)b.nx / (uint32_t)b.ny);
-        k.voxels = r[0];
+    for (int a = 0; a < 3; a++) {
+        k.lo[a] = o[a] + (int32_t)r[1 + a];
+        k.hi[a] = o[a] + (int32_t)r[4 + a] + 1;
     }
+    const uint32_t n = r[7];
+    k.seed[0] = b.x0 + (int32_t)(n % (uint32_t)b.nx);
+    k.seed[1] = b.y0 + (int32_t)(n / (uint32_t)b.nx % (uint32_t)b.ny);
+    k.seed[2] = b.z0 + (int32_t)(n / (uint32_t)b.nx / (uint32_t)b.ny);
+    k.voxels = r[0];
+    return k;
+}
+
+// The kernels' passes, word after word: gather, init, merge, flatten (roots take their slots), stats.  mask
+// may be NULL.
+void detach_host_query(const LinearWorld& w, const DetachBox& b, uint32_t* mask, DetachHost& q) {
+    const uint32_t V = b.voxels(), NW = b.words();
+    std::vector<uint32_t>&W = q.W, &D = q.D, &L = q.L, &slot = q.slot, &rec = q.rec;
+    W.assign(NW, 0); D.assign(NW, 0); L.assign((size_t)V + 1, 0); slot.assign(V, 0); rec.clear();
+    for (uint32_t g = 0; g < NW; g++) W[g] = detach_gather_word(w, b, g);
+    L[0] = 0;
+    for (uint32_t g = 0; g < NW; g++) detach_init_word(L.data(), detach_word(b, g), W[g]);
+    for (uint32_t g = 0; g < NW; g++) detach_merge_word(w, b, W.data(), L.data(), g);
+    if (mask) std::memset(mask, 0, (size_t)((V + 31) / 32) * 4);
+    q.voxels = 0;
+    for (int pass = 0; pass < 2; pass++)   // flatten (roots take their slots), then stats
+        for (uint32_t g = 0; g < NW; g++) {
+            const DetachWord d = detach_word(b, g);
+            uint32_t m = W[g], s, len;
+            while (detach_next_run(m, s, len)) {
+                const uint32_t p = d.base + s;
+                if (pass == 0) {
+                    const uint32_t r = detach_find(L.data(), p);
+                    for (uint32_t k = 0; k < len; k++) L[p + k] = r;
+                    if (r == p) {
+                        slot[p - 1] = (uint32_t)(rec.size() / DETACH_REC);
+                        const uint32_t init[DETACH_REC] = {0, ~0u, ~0u, ~0u, 0, 0, 0, p - 1};
+                        rec.insert(rec.end(), init, init + DETACH_REC);
+                    }
+                    continue;
+                }
+                const uint32_t r = L[p];
+                if (r == 0) continue;
+                q.voxels += len;
+                D[g] |= detach_low_bits(len) << s;
+                if (mask)
+                    for (uint32_t k = 0; k < len; k++) mask[(p - 1 + k) >> 5] |= 1u << ((p - 1 + k) & 31u);
+                uint32_t* t = rec.data() + (size_t)DETACH_REC * slot[r - 1];
+                const uint32_t lo[3] = {32u * (uint32_t)d.wx + s, (uint32_t)d.yl, (uint32_t)d.zl};
+                t[0] += len;
+                for (int a = 0; a < 3; a++) {
+                    t[1 + a] = std::min(t[1 + a], lo[a]);
+                    t[4 + a] = std::max(t[4 + a], a == 0 ? lo[0] + len - 1 : lo[a]);
+                }
+            }
+        }
+}
+
+namespace {
+
+// The nc records in ascending order of their seeds as rv_component: the first min(cap, nc) of them.
+void write_components(const DetachBox& b, const uint32_t* rec, uint32_t nc, rv_component* comps, int64_t cap) {
+    const std::vector<uint32_t> order = detach_seed_order(rec, nc);
+    for (int64_t i = 0; i < std::min<int64_t>(cap, nc); i++) comps[i] = detach_component(b, rec + (size_t)DETACH_REC * order[i]);
 }
 
 }  // namespace
@@ -50,7 +105,7 @@ extern "C" {
 rv_status rv_world_detached(rv_ctx* c, const rv_voxel_box* box, int32_t flags, rv_component* comps, int64_t cap,
                             int64_t* n_comps, uint64_t* n_voxels, uint32_t* mask, size_t mask_bytes) {
     if (!c) return RV_ERR_INVALID;
-    if (!args_ok(1 << c->lx, 1 << c->ly, 1 << c->lz, box, flags, comps, cap, mask, mask_bytes))
+    if (!detach_args_ok(1 << c->lx, 1 << c->ly, 1 << c->lz, box, flags, comps, cap, mask, mask_bytes))
         return fail(c, RV_ERR_INVALID, "rv_world_detached: bad box, flags, cap or array");
     if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_world_detached before a world build or import");
     const DetachBox b = detach_box(*box);
@@ -117,52 +172,15 @@ rv_status rv_world_detached_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, c
                                const rv_voxel_box* box, rv_component* comps, int64_t cap, int64_t* n_comps,
                                uint64_t* n_voxels, uint32_t* mask, size_t mask_bytes) {
     if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !bits) return RV_ERR_INVALID;
-    if (!args_ok(1 << log2_x, 1 << log2_y, 1 << log2_z, box, 0, comps, cap, mask, mask_bytes)) return RV_ERR_INVALID;
+    if (!detach_args_ok(1 << log2_x, 1 << log2_y, 1 << log2_z, box, 0, comps, cap, mask, mask_bytes)) return RV_ERR_INVALID;
     const LinearWorld w = linear_world(log2_x, log2_y, log2_z, bits, nullptr);
     const DetachBox b = detach_box(*box);
-    const uint32_t V = b.voxels(), NW = b.words();
-    // the kernels' passes, word after word
-    std::vector<uint32_t> W(NW), L((size_t)V + 1), slot(V), rec;
-    for (uint32_t g = 0; g < NW; g++) W[g] = detach_gather_word(w, b, g);
-    L[0] = 0;
-    for (uint32_t g = 0; g < NW; g++) detach_init_word(L.data(), detach_word(b, g), W[g]);
-    for (uint32_t g = 0; g < NW; g++) detach_merge_word(w, b, W.data(), L.data(), g);
-    if (mask) std::memset(mask, 0, (size_t)((V + 31) / 32) * 4);
-    uint64_t nv = 0;
-    for (int pass = 0; pass < 2; pass++)   // flatten (roots take their slots), then stats
-        for (uint32_t g = 0; g < NW; g++) {
-            const DetachWord d = detach_word(b, g);
-            uint32_t m = W[g], s, len;
-            while (detach_next_run(m, s, len)) {
-                const uint32_t p = d.base + s;
-                if (pass == 0) {
-                    const uint32_t r = detach_find(L.data(), p);
-                    for (uint32_t k = 0; k < len; k++) L[p + k] = r;
-                    if (r == p) {
-                        slot[p - 1] = (uint32_t)(rec.size() / DETACH_REC);
-                        const uint32_t init[DETACH_REC] = {0, ~0u, ~0u, ~0u, 0, 0, 0, p - 1};
-                        rec.insert(rec.end(), init, init + DETACH_REC);
-                    }
-                    continue;
-                }
-                const uint32_t r = L[p];
-                if (r == 0) continue;
-                nv += len;
-                if (mask)
-                    for (uint32_t k = 0; k < len; k++) mask[(p - 1 + k) >> 5] |= 1u << ((p - 1 + k) & 31u);
-                uint32_t* q = rec.data() + (size_t)DETACH_REC * slot[r - 1];
-                const uint32_t lo[3] = {32u * (uint32_t)d.wx + s, (uint32_t)d.yl, (uint32_t)d.zl};
-                q[0] += len;
-                for (int a = 0; a < 3; a++) {
-                    q[1 + a] = std::min(q[1 + a], lo[a]);
-                    q[4 + a] = std::max(q[4 + a], a == 0 ? lo[0] + len - 1 : lo[a]);
-                }
-            }
-        }
-    const uint32_t nc = (uint32_t)(rec.size() / DETACH_REC);
-    write_components(b, rec.data(), nc, comps, cap);
+    DetachHost q;
+    detach_host_query(w, b, mask, q);
+    const uint32_t nc = (uint32_t)(q.rec.size() / DETACH_REC);
+    write_components(b, q.rec.data(), nc, comps, cap);
     if (n_comps) *n_comps = nc;
-    if (n_voxels) *n_voxels = nv;
+    if (n_voxels) *n_voxels = q.voxels;
     return RV_OK;
 }
 

@@ -9,7 +9,8 @@
 //   rv_scroll.cpp   the world window moved over the terrain (rv_world_scroll);
 //   rv_persist.cpp  edited columns kept across scrolls (rv_world_persist);
 //   rv_bodies.cpp   swept box collision against the voxel window (rv_world_bodies_move);
-//   rv_detached.cpp voxels an edit left floating, found and cleared (rv_world_detached).
+//   rv_detached.cpp voxels an edit left floating, found and cleared (rv_world_detached);
+//   rv_fall.cpp     detached components dropped in place (rv_world_fall).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -351,6 +352,10 @@ struct rv_ctx {
     DevBuf<uint32_t> detach_scratch;
     std::vector<uint32_t> detach_h;
     uint64_t detach_calls = 0, detach_scanned = 0, detach_cleared = 0;
+    // rv_world_fall (rv_fall.cpp): it works in detach_scratch, its clearances behind the query's layout; the
+    // host copy of the clearances and rv_world_fall_info's sums
+    std::vector<uint32_t> fall_h;
+    uint64_t fall_calls = 0, fall_comps = 0, fall_voxels = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;
@@ -557,6 +562,21 @@ RV_HIDDEN rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n);
 // frames, written the bits and marked the columns: geom_ver, the exits (world_top), the local CSDF rebuild
 // and mark_world or the whole-grid build, whichever visits fewer cells, and rv_world_edit_info's record
 RV_HIDDEN rv_status edit_finish(rv_ctx* c, const int lo[3], const int hi[3]);
+
+// rv_detached.cpp: what rv_world_fall shares with rv_world_detached -- the check of the box, flags, cap and
+// arrays; the slots of nc component records in ascending order of their seeds and one record as rv_component
+// in window coordinates; and the host form of the query: the kernels' passes word after word, which leave what
+// launch_detach_query leaves on the device (include/rvgrt/rv_detached.h)
+namespace rv { struct DetachBox; }
+struct DetachHost {
+    std::vector<uint32_t> W, D, L, slot, rec;
+    uint64_t voxels = 0;   // detached
+};
+RV_HIDDEN bool detach_args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const void* comps, int64_t cap,
+                              const uint32_t* mask, size_t mask_bytes);
+RV_HIDDEN std::vector<uint32_t> detach_seed_order(const uint32_t* rec, uint32_t nc);
+RV_HIDDEN rv_component detach_component(const rv::DetachBox& b, const uint32_t* r);
+RV_HIDDEN void detach_host_query(const LinearWorld& w, const rv::DetachBox& b, uint32_t* mask, DetachHost& q);
 
 // rv_persist.cpp: the marking, capturing and restoring that rv_world_edit, rv_world_import, rv_world_build
 // and rv_world_scroll do while persistence is on (every one returns at once while it is off).  A range is

@@ -219,6 +219,41 @@ def detached_at(log2_dims, bits, box, cap=None, want_mask=True):
     return comps[:min(int(cap), int(n.value))].copy(), int(n.value), int(v.value), mask
 
 
+# an array of rv_fallen
+FALLEN_DTYPE = np.dtype([("comp", COMPONENT_DTYPE), ("fall", np.int32), ("flags", np.uint32)])
+
+
+def _box_tuple(b):
+    return (b.x0, b.y0, b.z0, b.x1, b.y1, b.z1)
+
+
+def fall_at(log2_dims, bits, box, max_fall=0, cap=None, want_bits=True, in_place=False):
+    """rv_world_fall_at (host only): the move of StateRender.world_fall evaluated on the CPU over
+    `bits` (RV_WORLD_BITS layout, log2_x >= 5) by the functions the kernels call.  Returns
+    (components, n_comps, n_voxels, changed, bits_out): FALLEN_DTYPE records (cap None = every
+    component), the totals, the changed voxel box as a tuple and the world after the move (None
+    unless want_bits; in_place writes it over `bits`, which must then be a contiguous uint32 array)."""
+    L = _lib.load()
+    src = np.ascontiguousarray(bits, np.uint32)
+    if src.size != (1 << sum(int(v) for v in log2_dims)) // 32:
+        raise ValueError("bits does not match log2_dims")
+    if in_place and src is not bits:
+        raise ValueError("in_place needs a contiguous uint32 array")
+    b = _voxel_box(box)
+    lg = [int(v) for v in log2_dims]
+    if cap is None:
+        cap = (_box_volume(b) + 1) // 2
+    comps = np.zeros(max(int(cap), 1), FALLEN_DTYPE)
+    out = src if in_place else (np.zeros_like(src) if want_bits else None)
+    n, v, ch = C.c_int64(), C.c_uint64(), rv_voxel_box()
+    st = L.rv_world_fall_at(lg[0], lg[1], lg[2], _ptr(src), C.byref(b), int(max_fall), _ptr(comps) if cap else None,
+                            int(cap), C.byref(n), C.byref(v), C.byref(ch), None if out is None else _ptr(out),
+                            0 if out is None else out.nbytes)
+    if st != 0:
+        raise RvError(f"rv_world_fall_at: {_lib.STATUS_NAMES.get(st, st)}")
+    return comps[:min(int(cap), int(n.value))].copy(), int(n.value), int(v.value), _box_tuple(ch), out
+
+
 def rccl_path():
     """The RCCL of the HIP runtime this process uses: torch's bundled librccl
     when torch is already imported (the library then shares torch's runtime),
@@ -624,6 +659,46 @@ class StateRender:
         self._check(self._L.rv_world_detached_info(self._h, C.byref(n), C.byref(s), C.byref(k)),
                     "rv_world_detached_info")
         return int(n.value), int(s.value), int(k.value)
+
+    def world_fall(self, box, max_fall=0, cap=None):
+        """rv_world_fall: every detached component of the voxel box drops straight down until a voxel
+        that does not move with it, or the floor, stops it (max_fall > 0: at most that many rows).
+        One call is one round, judged on the world before the call.  Returns (components, n_comps,
+        n_voxels, changed): FALLEN_DTYPE records (comp as before the move, fall, flags; cap None =
+        room for the most a box can hold), the totals, and the voxel box that bounds every cleared
+        and every set voxel (all zero when nothing moved).  Ends like the world_edit of the same
+        change; relight over `changed`.  Synchronous."""
+        b = _voxel_box(box)
+        if cap is None:   # the call runs once
+            cap = (_box_volume(b) + 1) // 2
+        comps = np.zeros(max(int(cap), 1), FALLEN_DTYPE)
+        n, v, ch = C.c_int64(), C.c_uint64(), rv_voxel_box()
+        self._check(self._L.rv_world_fall(self._h, C.byref(b), int(max_fall), _ptr(comps) if cap else None, int(cap),
+                                          C.byref(n), C.byref(v), C.byref(ch)), "rv_world_fall")
+        return comps[:min(int(cap), int(n.value))].copy(), int(n.value), int(v.value), _box_tuple(ch)
+
+    def world_fall_info(self):
+        """(calls, components_moved, voxels_moved): sums over the world_fall calls that ran."""
+        n, k, v = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._L.rv_world_fall_info(self._h, C.byref(n), C.byref(k), C.byref(v)), "rv_world_fall_info")
+        return int(n.value), int(k.value), int(v.value)
+
+    def world_settle(self, box, max_fall=0, max_rounds=64):
+        """world_fall repeated, each call over the `changed` box of the one before, until a call finds
+        nothing detached (or max_rounds calls have moved something).  Returns (rounds, box): the
+        calls that moved something and the union of their changed boxes (all zero for none).  A
+        changed box grows downwards with the fall; one above RV_DETACHED_MAX_VOXELS raises RvError."""
+        rounds, union = 0, None
+        box = tuple(int(v) for v in box)
+        while rounds < max_rounds:
+            _, n, _, changed = self.world_fall(box, max_fall, cap=0)
+            if n == 0:
+                break
+            rounds += 1
+            union = changed if union is None else (tuple(min(a, c) for a, c in zip(union[:3], changed[:3])) +
+                                                   tuple(max(a, c) for a, c in zip(union[3:], changed[3:])))
+            box = changed
+        return rounds, union or (0, 0, 0, 0, 0, 0)
 
     def gi_relight(self, box, frame0, iterations, init=False):
         """rv_gi_relight: `iterations` update steps (RNG frames frame0, frame0 + 1, ...)
