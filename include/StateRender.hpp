@@ -82,6 +82,12 @@ public:
     // Place / break blocks (no reference counterpart: its world is fixed after CArray::fill): voxel
     // boxes set or cleared in place, the CSDF and the early exits rebuilt around them (rv_world_edit)
     void editWorld(const rv_edit_box* boxes, int n) { check(rv_world_edit(ctx_, boxes, n), ctx_, "rv_world_edit"); }
+    // Craters, shafts, domes, boulders: ellipsoids and axis-aligned elliptic cylinders (half-voxel centre and
+    // radii) set or cleared in order by one launch, clipped to the window; the voxels that turned solid / empty
+    // into *set / *cleared (rv_world_edit_shapes)
+    void editShapes(const rv_edit_shape* shapes, int n, uint64_t* set = nullptr, uint64_t* cleared = nullptr) {
+        check(rv_world_edit_shapes(ctx_, shapes, n, set, cleared), ctx_, "rv_world_edit_shapes");
+    }
     // What an edit left floating in a voxel box: up to cap components into comps, their total returned; with
     // RV_DETACHED_CLEAR they are cleared like an editWorld of those voxels (rv_world_detached)
     int64_t findDetached(const rv_voxel_box& box, int flags, rv_component* comps, int64_t cap, uint64_t* voxels = nullptr) {

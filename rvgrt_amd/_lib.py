@@ -69,6 +69,16 @@ class rv_edit_box(C.Structure):
 RV_EDIT_MAX_BOXES = 1024
 
 
+class rv_edit_shape(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("solid", C.c_int32), ("c2", C.c_int32 * 3), ("r2", C.c_int32 * 3)]
+
+
+# rv_edit_shape.kind; the caps on a list and on a radius (half-voxels)
+RV_SHAPE_ELLIPSOID, RV_SHAPE_CYLINDER_X, RV_SHAPE_CYLINDER_Y, RV_SHAPE_CYLINDER_Z = range(4)
+RV_EDIT_MAX_SHAPES = 256
+RV_SHAPE_MAX_R2 = 512
+
+
 class rv_gi_box(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("z0", C.c_int32),
                 ("x1", C.c_int32), ("y1", C.c_int32), ("z1", C.c_int32)]
@@ -159,6 +169,9 @@ SIGNATURES = [
     ("rv_world_edit_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     ("rv_world_edit_region", I32, [I32, I32, I32, C.POINTER(rv_edit_box), I32, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_uint64)]),
+    ("rv_world_edit_shapes", I32, [P, P, I32, C.POINTER(U64), C.POINTER(U64)]),
+    ("rv_world_edit_shapes_at", I32, [I32, I32, I32, P, P, I32, C.POINTER(U64), C.POINTER(U64)]),
+    ("rv_world_edit_shapes_box", I32, [I32, I32, I32, P, I32, P, P]),
     ("rv_gi_relight", I32, [P, C.POINTER(rv_gi_box), U32, I32, I32]),
     ("rv_gi_relight_info", I32, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("rv_gi_relight_box", I32, [I32, I32, I32, C.POINTER(rv_edit_box), I32, I32, C.POINTER(rv_gi_box)]),

@@ -10,7 +10,8 @@
 //   rv_persist.cpp  edited columns kept across scrolls (rv_world_persist);
 //   rv_bodies.cpp   swept box collision against the voxel window (rv_world_bodies_move);
 //   rv_detached.cpp voxels an edit left floating, found and cleared (rv_world_detached);
-//   rv_fall.cpp     detached components dropped in place (rv_world_fall).
+//   rv_fall.cpp     detached components dropped in place (rv_world_fall);
+//   rv_shapes.cpp   ellipsoid and cylinder edits in one launch (rv_world_edit_shapes).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -356,6 +357,12 @@ struct rv_ctx {
     // host copy of the clearances and rv_world_fall_info's sums
     std::vector<uint32_t> fall_h;
     uint64_t fall_calls = 0, fall_comps = 0, fall_voxels = 0;
+    // rv_world_edit_shapes (rv_shapes.cpp): the shapes' device copy, the stable host copy it is uploaded from
+    // with the shapes' clipped boxes, and the two 64-bit sums (voxels turned on, turned off) the kernel adds to
+    std::vector<rv_edit_shape> shape_h;
+    std::vector<rv_voxel_box> shape_box_h;
+    DevBuf<rv_edit_shape> shape_list;
+    DevBuf<unsigned long long> shape_counts;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;

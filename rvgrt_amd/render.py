@@ -14,8 +14,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (RvError, rv_camera, rv_config, rv_edit_box, rv_frame_desc, rv_gi_box, rv_hit, rv_stats,
-                   rv_voxel_box)
+from ._lib import (RvError, rv_camera, rv_config, rv_edit_box, rv_edit_shape, rv_frame_desc, rv_gi_box, rv_hit,
+                   rv_stats, rv_voxel_box)
 
 
 def _ptr(a: np.ndarray):
@@ -77,6 +77,76 @@ def edit_region(log2_dims, boxes):
     if st != 0:
         raise RvError(f"rv_world_edit_region: {_lib.STATUS_NAMES.get(st, st)}")
     return tuple(region), int(cells.value)
+
+
+def _edit_shapes(shapes):
+    """ctypes array of rv_edit_shape from tuples (kind, solid, c2, r2), c2 and r2 being three half-voxel
+    values each."""
+    arr = (rv_edit_shape * max(len(shapes), 1))()
+    for i, s in enumerate(shapes):
+        if len(s) != 4 or len(s[2]) != 3 or len(s[3]) != 3:
+            raise ValueError("an edit shape is (kind, solid, (cx2, cy2, cz2), (rx2, ry2, rz2))")
+        arr[i] = rv_edit_shape(int(s[0]), int(s[1]), (C.c_int32 * 3)(*(int(v) for v in s[2])),
+                               (C.c_int32 * 3)(*(int(v) for v in s[3])))
+    return arr
+
+
+def edit_shapes_at(log2_dims, bits, shapes):
+    """rv_world_edit_shapes_at (host only): StateRender.world_edit_shapes evaluated on the CPU by the
+    row function the kernel calls, over a copy of `bits` (RV_WORLD_BITS layout, log2_x >= 5).  Returns
+    (bits_after, n_set, n_cleared)."""
+    L = _lib.load()
+    out = np.array(bits, np.uint32, copy=True).reshape(-1)
+    if out.size != (1 << sum(int(v) for v in log2_dims)) // 32:
+        raise ValueError("bits does not match log2_dims")
+    shapes = list(shapes)
+    lg = [int(v) for v in log2_dims]
+    a, b = C.c_uint64(), C.c_uint64()
+    st = L.rv_world_edit_shapes_at(lg[0], lg[1], lg[2], _ptr(out), _edit_shapes(shapes), len(shapes), C.byref(a),
+                                   C.byref(b))
+    if st != 0:
+        raise RvError(f"rv_world_edit_shapes_at: {_lib.STATUS_NAMES.get(st, st)}")
+    return out, int(a.value), int(b.value)
+
+
+def edit_shapes_box(log2_dims, shapes):
+    """rv_world_edit_shapes_box (host only): (each, all) -- the clipped voxel box (x0, y0, z0, x1, y1,
+    z1) of every shape in a world of these log2 dims (all zero for an empty one) and their union."""
+    L = _lib.load()
+    shapes = list(shapes)
+    lg = [int(v) for v in log2_dims]
+    each = (rv_voxel_box * max(len(shapes), 1))()
+    u = rv_voxel_box()
+    st = L.rv_world_edit_shapes_box(lg[0], lg[1], lg[2], _edit_shapes(shapes), len(shapes), each, C.byref(u))
+    if st != 0:
+        raise RvError(f"rv_world_edit_shapes_box: {_lib.STATUS_NAMES.get(st, st)}")
+    return [_box_tuple(each[i]) for i in range(len(shapes))], _box_tuple(u)
+
+
+def settle_parts(box, dims, cap=_lib.RV_DETACHED_MAX_VOXELS):
+    """The voxel boxes world_blast settles after clearing a shape whose clipped box is `box` in a window
+    of `dims` voxels: the box grown by 1 voxel per side and clipped to the window, halved along its
+    longest axis (the lower half getting the smaller share of an odd length) until no part holds more
+    than `cap` voxels, which is what rv_world_detached and rv_world_fall take.  The parts tile the grown
+    box without overlap.  Settling in parts is not settling the whole: each part is judged on its own,
+    and whatever reaches solid matter beyond a part stays, so a loose piece that straddles a cut holds
+    itself up from the other side and does not fall.  An empty box gives no parts."""
+    if _box_volume(_voxel_box(box)) == 0:
+        return []
+    parts = [tuple(max(int(box[a]) - 1, 0) for a in range(3)) +
+             tuple(min(int(box[3 + a]) + 1, int(dims[a])) for a in range(3))]
+    while any(_box_volume(_voxel_box(p)) > cap for p in parts):
+        nxt = []
+        for p in parts:
+            if _box_volume(_voxel_box(p)) <= cap:
+                nxt.append(p)
+                continue
+            a = max(range(3), key=lambda k: p[3 + k] - p[k])
+            mid = (p[a] + p[3 + a]) // 2
+            nxt.append(p[:3 + a] + (mid,) + p[4 + a:])
+            nxt.append(p[:a] + (mid,) + p[a + 1:])
+        parts = nxt
+    return parts
 
 
 def relight_box(log2_dims, boxes, margin=0):
@@ -501,6 +571,49 @@ class StateRender:
         of the edited world would leave them."""
         boxes = list(boxes)
         self._check(self._L.rv_world_edit(self._h, _edit_boxes(boxes), len(boxes)), "rv_world_edit")
+
+    def world_edit_shapes(self, shapes):
+        """rv_world_edit_shapes: set / clear ellipsoids and axis-aligned elliptic cylinders (kind, solid,
+        c2, r2) -- centre and radii in half-voxels, voxel x having its centre at 2 x + 1 -- in place, in
+        order, by one launch; shapes are clipped to the window.  Ends like world_edit over the union of
+        their boxes (edit_shapes_box).  Returns (n_set, n_cleared): the voxels that turned solid and the
+        voxels that turned empty, world before against world after."""
+        shapes = list(shapes)
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self._L.rv_world_edit_shapes(self._h, _edit_shapes(shapes), len(shapes), C.byref(a), C.byref(b)),
+                    "rv_world_edit_shapes")
+        return int(a.value), int(b.value)
+
+    def world_blast(self, centre_voxel, radius_voxels, settle=True, relight=0):
+        """An explosion, composed of existing calls: world_edit_shapes clears the sphere of
+        `radius_voxels` around the centre of voxel `centre_voxel`; with `settle`, world_settle lets what
+        it cut loose come down, over the parts settle_parts makes of the sphere's clipped box -- the box
+        grown by 1 voxel, whole up to a radius of about 62 voxels, in halves above that, where a loose
+        piece that straddles a cut stays up (see there); with relight > 0, gi_relight runs
+        that many steps (frame0 = 0, INIT) over relight_box (margin 1) of everything that changed.
+        Returns a dict: "edit" (n_set, n_cleared), "box" the sphere's clipped box, "settle" a list of
+        world_settle's (rounds, box) per part (None without settle), "relight" the GI box (or None)."""
+        r2 = 2 * int(radius_voxels)
+        shape = (_lib.RV_SHAPE_ELLIPSOID, 0, tuple(2 * int(v) + 1 for v in centre_voxel), (r2, r2, r2))
+        edit = self.world_edit_shapes([shape])
+        _, box = edit_shapes_box(self.log2_dims, [shape])
+        out = {"edit": edit, "box": box, "settle": None, "relight": None}
+        changed = [box] if edit[1] else []
+        if settle and _box_volume(_voxel_box(box)) > 0:
+            parts = settle_parts(box, self.dims)
+            out["settle"] = [self.world_settle(p) for p in parts]
+            changed += [b for rounds, b in out["settle"] if rounds]
+        if relight > 0 and changed:
+            gbox = relight_box(self.log2_dims, [b + (0,) for b in changed], margin=1)
+            cells = (gbox[3] - gbox[0]) * (gbox[4] - gbox[1]) * (gbox[5] - gbox[2])
+            step = max(_lib.RV_RELIGHT_MAX_RECORDS // max(cells, 1), 1)   # k1 then k2 steps equal k1 + k2
+            done = 0
+            while done < int(relight):
+                k = min(step, int(relight) - done)
+                self.gi_relight(gbox, done, k, init=done == 0)
+                done += k
+            out["relight"] = gbox
+        return out
 
     def world_edit_info(self):
         """(edits, csdf_cells, last_full): calls that changed a voxel, the coarse
