@@ -27,13 +27,25 @@
 //     continues with (old, b).  Each round replaces the larger of (a, b) by a smaller node, so a + b falls
 //     strictly: no lane ever waits for another.
 #pragma once
-#include "../rvgrt.h"
-#include "rv_device.h"
+#include "rv_internal.h"
 
 namespace rv {
 
-constexpr uint32_t DETACH_REC = 8;   // dwords of a component record: voxels, min x y z, max x y z (box-local), seed n
+// the kernels' sums / minima / maxima over the 64 lanes of a wave (every lane active)
+__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = umin(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o); v = v > t ? v : t; }
+    return v;
+}
 
+// (a component record: DETACH_REC dwords, on the host a DetachRec -- rv_words.h)
 struct DetachBox {
     int x0, y0, z0, nx, ny, nz, nwx;
     RV_HD uint32_t voxels() const { return (uint32_t)nx * (uint32_t)ny * (uint32_t)nz; }   // <= 2^21
@@ -201,9 +213,10 @@ RV_HD void detach_merge_word(const WV& w, const DetachBox& b, const uint32_t* W,
 struct DetachLayout {
     size_t cnt, mask, W, D, L, slot, rec, total;
 };
+inline size_t detach_up64(size_t v) { return (v + 63) & ~(size_t)63; }   // whole 256-B lines
 inline DetachLayout detach_layout(const DetachBox& b) {
     const size_t V = b.voxels(), NW = b.words();
-    auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    const auto up = detach_up64;
     DetachLayout l;
     l.cnt = 0;
     l.mask = 64;
@@ -217,9 +230,9 @@ inline DetachLayout detach_layout(const DetachBox& b) {
 }
 
 // rv_detached.hip: the five passes of the query over scratch laid out as above (counters and mask zeroed
-// here), and the clear of the detached bits D inside the voxel box [lo, hi) of B
+// here), and the clear of the detached bits D inside the voxel box `box` of B
 void launch_detach_query(hipStream_t s, const World& w, const DetachBox& b, uint32_t* scratch);
 void launch_detach_clear(hipStream_t s, uint32_t* brick, const World& w, const DetachBox& b, const uint32_t* D,
-                         const int lo[3], const int hi[3]);
+                         const rv_voxel_box& box);
 
 }  // namespace rv

@@ -2,7 +2,7 @@
 // an ellipsoid or an axis-aligned elliptic cylinder contains, as integer functions that k_edit_shapes
 // (rv_shapes.hip) runs one lane per brick word and that rv_world_edit_shapes_at runs on the CPU over
 // RV_WORLD_BITS words -- the validation, the clipped bounding box, the 8-bit mask of one row of one word, and
-// the host evaluation itself.  The header needs only <stdint.h> and include/rvgrt.h: a program can use the
+// the host evaluation itself.  The header needs only <stdint.h>, include/rvgrt.h and rv_words.h: a program can use the
 // host evaluation without the HIP runtime (tests/host_shapes).
 //
 // Everything is in half-voxels: voxel v has its centre at 2 v + 1, d = 2 v + 1 - c2, q = r2 * r2.
@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../rvgrt.h"
+#include "rv_words.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define RV_SHAPES_HD __host__ __device__ inline
@@ -130,20 +131,16 @@ RV_SHAPES_HD uint32_t shape_row_mask(const rv_edit_shape& s, int32_t y, int32_t 
 inline bool shapes_boxes(int lx, int ly, int lz, const rv_edit_shape* s, int32_t n, rv_voxel_box* each,
                          rv_voxel_box* all) {
     const int32_t D[3] = {1 << lx, 1 << ly, 1 << lz};
-    int32_t ulo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, uhi[3] = {0, 0, 0};
-    bool any = false;
+    rv_voxel_box u = empty_box();
     for (int32_t i = 0; i < n; i++) {
         int32_t lo[3], hi[3];
         const bool ok = shape_box(s[i], D, lo, hi);
-        if (each) each[i] = ok ? rv_voxel_box{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]} : rv_voxel_box{0, 0, 0, 0, 0, 0};
-        if (!ok) continue;
-        any = true;
-        for (int a = 0; a < 3; a++) {
-            ulo[a] = lo[a] < ulo[a] ? lo[a] : ulo[a];
-            uhi[a] = hi[a] > uhi[a] ? hi[a] : uhi[a];
-        }
+        const rv_voxel_box b = ok ? rv_voxel_box{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]} : rv_voxel_box{0, 0, 0, 0, 0, 0};
+        if (each) each[i] = b;
+        if (ok) box_include(u, b);
     }
-    *all = any ? rv_voxel_box{ulo[0], ulo[1], ulo[2], uhi[0], uhi[1], uhi[2]} : rv_voxel_box{0, 0, 0, 0, 0, 0};
+    const bool any = u.x1 > u.x0;
+    *all = any ? u : rv_voxel_box{0, 0, 0, 0, 0, 0};
     return any;
 }
 

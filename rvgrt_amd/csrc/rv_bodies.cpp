@@ -60,7 +60,7 @@ rv_status rv_world_bodies_info(rv_ctx* c, uint64_t* calls, uint64_t* bodies) {
 
 rv_status rv_world_bodies_move_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, const uint32_t* bits, const rv_body* in,
                                   int64_t n, int32_t flags, rv_body_out* out) {
-    if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !bits || !args_ok(in, n, flags, out)) return RV_ERR_INVALID;
+    if (!linear_dims_ok(log2_x, log2_y, log2_z) || !bits || !args_ok(in, n, flags, out)) return RV_ERR_INVALID;
     const LinearWorld w = linear_world(log2_x, log2_y, log2_z, bits, nullptr);
     const bool open = (flags & RV_BODIES_OPEN_EDGES) != 0;
     for (int64_t i = 0; i < n; i++) {

@@ -8,48 +8,41 @@
 
 static_assert(sizeof(rv_component) == 40 && sizeof(rv_voxel_box) == 24, "rv_component / rv_voxel_box layout");
 
-// shared with rv_fall.cpp (declared in rv_host.h): the argument check, the records' order and conversion, and
-// the host form of the query
+// shared with rv_fall.cpp (declared in rv_host.h): the argument check, the records' order and conversion, the
+// host form of the query and the device form's opening
 bool detach_args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const void* comps, int64_t cap,
                     const uint32_t* mask, size_t mask_bytes) {
     if (!b || (flags & ~RV_DETACHED_CLEAR) || cap < 0 || (cap > 0 && !comps)) return false;
-    if (b->x0 < 0 || b->y0 < 0 || b->z0 < 0 || b->x1 > X || b->y1 > Y || b->z1 > Z) return false;
-    if (b->x1 <= b->x0 || b->y1 <= b->y0 || b->z1 <= b->z0) return false;
+    if (!voxel_box_ok(X, Y, Z, *b)) return false;
     const uint64_t V = (uint64_t)(b->x1 - b->x0) * (uint64_t)(b->y1 - b->y0) * (uint64_t)(b->z1 - b->z0);
     if (V > RV_DETACHED_MAX_VOXELS) return false;
     return !mask || mask_bytes >= 4 * ((V + 31) / 32);
 }
 
-// the slots of nc records (DETACH_REC dwords each) in ascending order of their seeds
-std::vector<uint32_t> detach_seed_order(const uint32_t* rec, uint32_t nc) {
+// the slots of nc records in ascending order of their seeds
+std::vector<uint32_t> detach_seed_order(const DetachRec* rec, uint32_t nc) {
     std::vector<uint32_t> order(nc);
     for (uint32_t i = 0; i < nc; i++) order[i] = i;
-    std::sort(order.begin(), order.end(),
-              [&](uint32_t p, uint32_t q) { return rec[DETACH_REC * p + 7] < rec[DETACH_REC * q + 7]; });
+    std::sort(order.begin(), order.end(), [&](uint32_t p, uint32_t q) { return rec[p].seed < rec[q].seed; });
     return order;
 }
 
 // one box-local record as rv_component in window coordinates
-rv_component detach_component(const DetachBox& b, const uint32_t* r) {
-    rv_component k;
-    const int o[3] = {b.x0, b.y0, b.z0};
-    for (int a = 0; a < 3; a++) {
-        k.lo[a] = o[a] + (int32_t)r[1 + a];
-        k.hi[a] = o[a] + (int32_t)r[4 + a] + 1;
-    }
-    const uint32_t n = r[7];
-    k.seed[0] = b.x0 + (int32_t)(n % (uint32_t)b.nx);
-    k.seed[1] = b.y0 + (int32_t)(n / (uint32_t)b.nx % (uint32_t)b.ny);
-    k.seed[2] = b.z0 + (int32_t)(n / (uint32_t)b.nx / (uint32_t)b.ny);
-    k.voxels = r[0];
-    return k;
+rv_component detach_component(const DetachBox& b, const DetachRec& r) {
+    const rv_voxel_box v = detach_rec_box(b, r);
+    const uint32_t n = r.seed;
+    return rv_component{{v.x0, v.y0, v.z0}, {v.x1, v.y1, v.z1},
+                        {b.x0 + (int32_t)(n % (uint32_t)b.nx), b.y0 + (int32_t)(n / (uint32_t)b.nx % (uint32_t)b.ny),
+                         b.z0 + (int32_t)(n / (uint32_t)b.nx / (uint32_t)b.ny)},
+                        r.voxels};
 }
 
 // The kernels' passes, word after word: gather, init, merge, flatten (roots take their slots), stats.  mask
 // may be NULL.
 void detach_host_query(const LinearWorld& w, const DetachBox& b, uint32_t* mask, DetachHost& q) {
     const uint32_t V = b.voxels(), NW = b.words();
-    std::vector<uint32_t>&W = q.W, &D = q.D, &L = q.L, &slot = q.slot, &rec = q.rec;
+    std::vector<uint32_t>&W = q.W, &D = q.D, &L = q.L, &slot = q.slot;
+    std::vector<DetachRec>& rec = q.rec;
     W.assign(NW, 0); D.assign(NW, 0); L.assign((size_t)V + 1, 0); slot.assign(V, 0); rec.clear();
     for (uint32_t g = 0; g < NW; g++) W[g] = detach_gather_word(w, b, g);
     L[0] = 0;
@@ -67,9 +60,8 @@ void detach_host_query(const LinearWorld& w, const DetachBox& b, uint32_t* mask,
                     const uint32_t r = detach_find(L.data(), p);
                     for (uint32_t k = 0; k < len; k++) L[p + k] = r;
                     if (r == p) {
-                        slot[p - 1] = (uint32_t)(rec.size() / DETACH_REC);
-                        const uint32_t init[DETACH_REC] = {0, ~0u, ~0u, ~0u, 0, 0, 0, p - 1};
-                        rec.insert(rec.end(), init, init + DETACH_REC);
+                        slot[p - 1] = (uint32_t)rec.size();
+                        rec.push_back(DetachRec{0, {~0u, ~0u, ~0u}, {0, 0, 0}, p - 1});
                     }
                     continue;
                 }
@@ -79,23 +71,43 @@ void detach_host_query(const LinearWorld& w, const DetachBox& b, uint32_t* mask,
                 D[g] |= detach_low_bits(len) << s;
                 if (mask)
                     for (uint32_t k = 0; k < len; k++) mask[(p - 1 + k) >> 5] |= 1u << ((p - 1 + k) & 31u);
-                uint32_t* t = rec.data() + (size_t)DETACH_REC * slot[r - 1];
+                DetachRec& t = rec[slot[r - 1]];
                 const uint32_t lo[3] = {32u * (uint32_t)d.wx + s, (uint32_t)d.yl, (uint32_t)d.zl};
-                t[0] += len;
+                t.voxels += len;
                 for (int a = 0; a < 3; a++) {
-                    t[1 + a] = std::min(t[1 + a], lo[a]);
-                    t[4 + a] = std::max(t[4 + a], a == 0 ? lo[0] + len - 1 : lo[a]);
+                    t.lo[a] = std::min(t.lo[a], lo[a]);
+                    t.hi[a] = std::max(t.hi[a], a == 0 ? lo[0] + len - 1 : lo[a]);
                 }
             }
         }
 }
 
+rv_status detach_run_query(rv_ctx* c, const DetachBox& b, size_t extra_dwords, uint32_t cnt[2]) {
+    const DetachLayout l = detach_layout(b);
+    if (rv_status s = c->detach_scratch.reserve(c, (l.total + extra_dwords) * 4)) return s;
+    // the last world write may have been issued on another stream
+    if (c->world_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_world, 0));
+    launch_detach_query(c->stream, current_world(c), b, c->detach_scratch);
+    LAUNCH_CHECK(c);
+    HIP_TRY(c, hipMemcpyAsync(cnt, c->detach_scratch + l.cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RV_OK;
+}
+
+rv_status detach_copy_records(rv_ctx* c, const DetachBox& b, uint32_t nc) {
+    c->detach_h.resize(nc);
+    if (nc)
+        HIP_TRY(c, hipMemcpyAsync(c->detach_h.data(), c->detach_scratch + detach_layout(b).rec, nc * sizeof(DetachRec),
+                                  hipMemcpyDeviceToHost, c->stream));
+    return RV_OK;
+}
+
 namespace {
 
 // The nc records in ascending order of their seeds as rv_component: the first min(cap, nc) of them.
-void write_components(const DetachBox& b, const uint32_t* rec, uint32_t nc, rv_component* comps, int64_t cap) {
+void write_components(const DetachBox& b, const DetachRec* rec, uint32_t nc, rv_component* comps, int64_t cap) {
     const std::vector<uint32_t> order = detach_seed_order(rec, nc);
-    for (int64_t i = 0; i < std::min<int64_t>(cap, nc); i++) comps[i] = detach_component(b, rec + (size_t)DETACH_REC * order[i]);
+    for (int64_t i = 0; i < std::min<int64_t>(cap, nc); i++) comps[i] = detach_component(b, rec[order[i]]);
 }
 
 }  // namespace
@@ -111,24 +123,15 @@ rv_status rv_world_detached(rv_ctx* c, const rv_voxel_box* box, int32_t flags, r
     const DetachBox b = detach_box(*box);
     const DetachLayout l = detach_layout(b);
     const uint32_t V = b.voxels();
-    if (rv_status s = c->detach_scratch.reserve(c, l.total * 4)) return s;
-    // the last world write may have been issued on another stream
-    if (c->world_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_world, 0));
-    launch_detach_query(c->stream, current_world(c), b, c->detach_scratch);
-    LAUNCH_CHECK(c);
     uint32_t cnt[2] = {0, 0};   // components, detached voxels
-    HIP_TRY(c, hipMemcpyAsync(cnt, c->detach_scratch + l.cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (rv_status s = detach_run_query(c, b, 0, cnt)) return s;
     const uint32_t nc = cnt[0];
-    c->detach_h.resize((size_t)DETACH_REC * nc);
-    if (nc)
-        HIP_TRY(c, hipMemcpyAsync(c->detach_h.data(), c->detach_scratch + l.rec, (size_t)DETACH_REC * nc * 4,
-                                  hipMemcpyDeviceToHost, c->stream));
+    if (rv_status s = detach_copy_records(c, b, nc)) return s;
     if (mask)
         HIP_TRY(c, hipMemcpyAsync(mask, c->detach_scratch + l.mask, (size_t)((V + 31) / 32) * 4, hipMemcpyDeviceToHost,
                                   c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    uint32_t* rec = c->detach_h.data();
+    const DetachRec* rec = c->detach_h.data();
     write_components(b, rec, nc, comps, cap);
     if (n_comps) *n_comps = nc;
     if (n_voxels) *n_voxels = cnt[1];
@@ -138,23 +141,14 @@ rv_status rv_world_detached(rv_ctx* c, const rv_voxel_box* box, int32_t flags, r
     rv_status st = RV_OK;
     if ((flags & RV_DETACHED_CLEAR) && cnt[1]) {
         // the voxel box of everything detached, and the columns under each component for persistence
-        int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {0, 0, 0};
-        const int o[3] = {b.x0, b.y0, b.z0};
-        for (uint32_t i = 0; i < nc; i++)
-            for (int a = 0; a < 3; a++) {
-                lo[a] = std::min(lo[a], o[a] + (int)rec[DETACH_REC * i + 1 + a]);
-                hi[a] = std::max(hi[a], o[a] + (int)rec[DETACH_REC * i + 4 + a] + 1);
-            }
+        rv_voxel_box all = empty_box();
+        for (uint32_t i = 0; i < nc; i++) box_include(all, detach_rec_box(b, rec[i]));
         if (rv_status ws = wait_all_frames(c)) return ws;
-        launch_detach_clear(c->stream, c->brick, current_world(c), b, c->detach_scratch + l.D, lo, hi);
+        launch_detach_clear(c->stream, c->brick, current_world(c), b, c->detach_scratch + l.D, all);
         LAUNCH_CHECK(c);
-        for (uint32_t i = 0; i < nc; i++) {
-            const uint32_t* r = rec + (size_t)DETACH_REC * i;
-            persist_mark(c, ColumnRange{(b.x0 + (int)r[1]) >> 3, ((b.x0 + (int)r[4]) >> 3) + 1, (b.z0 + (int)r[3]) >> 3,
-                                        ((b.z0 + (int)r[6]) >> 3) + 1});
-        }
+        for (uint32_t i = 0; i < nc; i++) persist_mark(c, columns_under(detach_rec_box(b, rec[i])));
         c->detach_cleared += cnt[1];
-        st = edit_finish(c, lo, hi);   // waits for the clear as well
+        st = edit_finish(c, all);   // waits for the clear as well
     }
     c->detach_scratch.trim(EDIT_SCRATCH_KEEP);
     return st;
@@ -171,13 +165,13 @@ rv_status rv_world_detached_info(rv_ctx* c, uint64_t* calls, uint64_t* voxels_sc
 rv_status rv_world_detached_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, const uint32_t* bits,
                                const rv_voxel_box* box, rv_component* comps, int64_t cap, int64_t* n_comps,
                                uint64_t* n_voxels, uint32_t* mask, size_t mask_bytes) {
-    if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !bits) return RV_ERR_INVALID;
+    if (!linear_dims_ok(log2_x, log2_y, log2_z) || !bits) return RV_ERR_INVALID;
     if (!detach_args_ok(1 << log2_x, 1 << log2_y, 1 << log2_z, box, 0, comps, cap, mask, mask_bytes)) return RV_ERR_INVALID;
     const LinearWorld w = linear_world(log2_x, log2_y, log2_z, bits, nullptr);
     const DetachBox b = detach_box(*box);
     DetachHost q;
     detach_host_query(w, b, mask, q);
-    const uint32_t nc = (uint32_t)(q.rec.size() / DETACH_REC);
+    const uint32_t nc = (uint32_t)q.rec.size();
     write_components(b, q.rec.data(), nc, comps, cap);
     if (n_comps) *n_comps = nc;
     if (n_voxels) *n_voxels = q.voxels;

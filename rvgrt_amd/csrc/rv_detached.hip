@@ -9,20 +9,6 @@
 
 namespace rv {
 
-// sums / minima / maxima over the 64 lanes of a wave (every lane active)
-__device__ __forceinline__ uint32_t wave_add(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = umin(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o); v = v > t ? v : t; }
-    return v;
-}
-
 // ================================================================ pass 1: gather
 __global__ void __launch_bounds__(256) k_detach_gather(World w, DetachBox b, uint32_t nwords, uint32_t* __restrict__ W) {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
@@ -131,16 +117,14 @@ __global__ void __launch_bounds__(256) k_detach_stats(DetachBox b, uint32_t nwor
 }
 
 // ================================================================ pass 6: clear
-// One lane per 32-bit brick word (8 x, 4 y, 1 z voxels) of the voxel box that bounds the detached voxels, as
-// k_edit_bits: the lane and-nots the word's detached voxels out and is the word's only writer.
+// One lane per word of the grid (WordGrid, rv_words.h) of the voxel box that bounds the detached voxels: the
+// lane and-nots the word's detached voxels out and is the word's only writer.
 __global__ void __launch_bounds__(256) k_detach_clear(uint32_t* __restrict__ brick, World w, DetachBox b,
-                                                      const uint32_t* __restrict__ D, int wx0, int wy0, int wz0, int nwy,
-                                                      int nwz, uint32_t nwords) {
+                                                      const uint32_t* __restrict__ D, WordGrid grid) {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g >= nwords) return;
-    const int z = wz0 + (int)(g % (uint32_t)nwz);
-    const uint32_t t = g / (uint32_t)nwz;
-    const int wy = wy0 + (int)(t % (uint32_t)nwy), wx = wx0 + (int)(t / (uint32_t)nwy);
+    if (g >= grid.nwords) return;
+    int wx, wy, z;
+    grid.word(g, wx, wy, z);
     const int xl = wx * 8 - b.x0, zl = z - b.z0;   // xl >= -7; zl inside B
     uint32_t clr = 0;
     for (int r = 0; r < 4; r++) {
@@ -159,12 +143,10 @@ __global__ void __launch_bounds__(256) k_detach_clear(uint32_t* __restrict__ bri
         clr |= byte << (8 * r);
     }
     if (!clr) return;
-    const uint64_t bi = bits_word_index(brick_of(w, wx, wy >> 1, z >> 3), (uint32_t)(wy & 1) | ((uint32_t)(z & 7) << 1));
-    brick[bi] &= ~clr;
+    brick[brick_word_index(w, wx, wy, z)] &= ~clr;
 }
 
 // ================================================================ launchers
-static inline uint32_t nblk(uint64_t n) { return (uint32_t)((n + 255) / 256); }
 
 void launch_detach_query(hipStream_t s, const World& w, const DetachBox& b, uint32_t* scratch) {
     const DetachLayout l = detach_layout(b);
@@ -180,12 +162,9 @@ void launch_detach_query(hipStream_t s, const World& w, const DetachBox& b, uint
 }
 
 void launch_detach_clear(hipStream_t s, uint32_t* brick, const World& w, const DetachBox& b, const uint32_t* D,
-                         const int lo[3], const int hi[3]) {
-    const int wx0 = lo[0] >> 3, wy0 = lo[1] >> 2, wz0 = lo[2];
-    const int nwx = ((hi[0] - 1) >> 3) - wx0 + 1, nwy = ((hi[1] - 1) >> 2) - wy0 + 1, nwz = hi[2] - wz0;
-    const uint32_t nwords = (uint32_t)nwx * (uint32_t)nwy * (uint32_t)nwz;   // <= 2^21 voxels' words
-    hipLaunchKernelGGL(k_detach_clear, dim3(nblk(nwords)), dim3(256), 0, s, brick, w, b, D, wx0, wy0, wz0, nwy, nwz,
-                       nwords);
+                         const rv_voxel_box& box) {
+    const WordGrid grid = word_grid(box);
+    hipLaunchKernelGGL(k_detach_clear, dim3(nblk(grid.nwords)), dim3(256), 0, s, brick, w, b, D, grid);
 }
 
 }  // namespace rv

@@ -8,14 +8,13 @@ bool dims_ok(int lx, int ly, int lz) {   // rv_create's limits
     return lx >= 4 && ly >= 4 && lz >= 4 && lx <= 13 && ly <= 13 && lz <= 13 && lx + ly + lz <= 34;
 }
 
+static rv_voxel_box edit_voxels(const rv_edit_box& b) { return rv_voxel_box{b.x0, b.y0, b.z0, b.x1, b.y1, b.z1}; }
+
 bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n) {
     if (n < 0 || n > RV_EDIT_MAX_BOXES || (n > 0 && !b)) return false;
     const int X = 1 << lx, Y = 1 << ly, Z = 1 << lz;
-    for (int i = 0; i < n; i++) {
-        if (b[i].x0 < 0 || b[i].y0 < 0 || b[i].z0 < 0 || b[i].x1 > X || b[i].y1 > Y || b[i].z1 > Z) return false;
-        if (b[i].x1 <= b[i].x0 || b[i].y1 <= b[i].y0 || b[i].z1 <= b[i].z0) return false;
-        if (b[i].solid != 0 && b[i].solid != 1) return false;
-    }
+    for (int i = 0; i < n; i++)
+        if (!voxel_box_ok(X, Y, Z, edit_voxels(b[i])) || (b[i].solid != 0 && b[i].solid != 1)) return false;
     return true;
 }
 
@@ -78,19 +77,19 @@ namespace {
 // each clipped to the world (a neighbour outside the world is skipped by the passes, Appendix R3).
 // Everything outside F keeps its byte: it equals what a whole-grid build would write there.
 struct EditPlan {
-    int lo[3], hi[3];        // voxel bounding box of the boxes, [lo, hi)
+    rv_voxel_box box;        // voxel bounding box of the boxes
     CsdfBoxes b;
     uint64_t local_cells;    // cells the four local passes visit
     uint64_t full_cells;     // cells the four whole-grid passes visit
 };
 
-// the plan of an edit whose voxels lie in [lo, hi)
-EditPlan edit_plan_box(int lx, int ly, int lz, const int lo[3], const int hi[3]) {
+// the plan of an edit whose voxels lie in box
+EditPlan edit_plan_box(int lx, int ly, int lz, const rv_voxel_box& box) {
     EditPlan p{};
-    for (int a = 0; a < 3; a++) { p.lo[a] = lo[a]; p.hi[a] = hi[a]; }
+    p.box = box;
     const int S[3] = {1 << (lx - 1), 1 << (ly - 1), 1 << (lz - 1)};
-    int e0[3], e1[3];
-    for (int a = 0; a < 3; a++) { e0[a] = p.lo[a] >> 1; e1[a] = ((p.hi[a] - 1) >> 1) + 1; }
+    const int e0[3] = {box.x0 >> 1, box.y0 >> 1, box.z0 >> 1};
+    const int e1[3] = {((box.x1 - 1) >> 1) + 1, ((box.y1 - 1) >> 1) + 1, ((box.z1 - 1) >> 1) + 1};
     p.b = csdf_boxes(e0, e1, S);
     p.local_cells = p.b.passes();
     p.full_cells = 4ull * (uint64_t)S[0] * (uint64_t)S[1] * (uint64_t)S[2];
@@ -99,22 +98,17 @@ EditPlan edit_plan_box(int lx, int ly, int lz, const int lo[3], const int hi[3])
 
 // boxes validated, n >= 1
 EditPlan edit_plan(int lx, int ly, int lz, const rv_edit_box* b, int n) {
-    int lo[3], hi[3];
-    for (int a = 0; a < 3; a++) { lo[a] = INT32_MAX; hi[a] = 0; }
-    for (int i = 0; i < n; i++) {
-        const int l[3] = {b[i].x0, b[i].y0, b[i].z0}, h[3] = {b[i].x1, b[i].y1, b[i].z1};
-        for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], l[a]); hi[a] = std::max(hi[a], h[a]); }
-    }
-    return edit_plan_box(lx, ly, lz, lo, hi);
+    rv_voxel_box all = empty_box();
+    for (int i = 0; i < n; i++) box_include(all, edit_voxels(b[i]));
+    return edit_plan_box(lx, ly, lz, all);
 }
 
 }  // namespace
 
-// What follows the bit writes of an edit whose changed voxels lie in [lo, hi) (the caller has waited for the
-// frames, written the bits and marked the columns for persistence): shared by rv_world_edit and
-// rv_world_detached's clear.
-rv_status edit_finish(rv_ctx* c, const int lo[3], const int hi[3]) {
-    const EditPlan p = edit_plan_box(c->lx, c->ly, c->lz, lo, hi);
+// What follows the bit writes of an edit whose changed voxels lie in `changed` (the caller has waited for the
+// frames, written the bits and marked the columns for persistence): shared by every in-place voxel write.
+rv_status edit_finish(rv_ctx* c, const rv_voxel_box& changed) {
+    const EditPlan p = edit_plan_box(c->lx, c->ly, c->lz, changed);
     c->edit_cells = 0;
     c->edit_full = 0;
     c->geom_ver++;
@@ -166,7 +160,7 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
     HIP_TRY(c, hipMemcpyAsync(c->edit_boxes, c->edit_h.data(), (size_t)n * sizeof(rv_edit_box), hipMemcpyHostToDevice,
                               c->stream));
     HIP_TRY(c, hipMemsetAsync(c->edit_flag, 0, 4, c->stream));
-    launch_edit_bits(c->stream, c->brick, current_world(c), c->edit_boxes, n, p.lo, p.hi, c->edit_flag);
+    launch_edit_bits(c->stream, c->brick, current_world(c), c->edit_boxes, n, p.box, c->edit_flag);
     LAUNCH_CHECK(c);
     uint32_t changed = 0;
     HIP_TRY(c, hipMemcpyAsync(&changed, c->edit_flag, 4, hipMemcpyDeviceToHost, c->stream));
@@ -176,9 +170,8 @@ rv_status rv_world_edit(rv_ctx* c, const rv_edit_box* boxes, int32_t n) {
     if (!changed) return RV_OK;   // every voxel already had its value: nothing to rebuild or invalidate
 
     for (int i = 0; i < n; i++)   // persistence: the columns under each box may now differ from the generator's
-        persist_mark(c, ColumnRange{boxes[i].x0 >> 3, ((boxes[i].x1 - 1) >> 3) + 1, boxes[i].z0 >> 3,
-                                    ((boxes[i].z1 - 1) >> 3) + 1});
-    return edit_finish(c, p.lo, p.hi);
+        persist_mark(c, columns_under(edit_voxels(boxes[i])));
+    return edit_finish(c, p.box);
 }
 
 rv_status rv_world_edit_info(rv_ctx* c, uint64_t* edits, uint64_t* csdf_cells, int32_t* last_full) {

@@ -7,19 +7,17 @@
 namespace rv {
 
 // ================================================================ bit write
-// One lane per 32-bit brick word (8 x, 4 y, 1 z voxels) of the voxel box that bounds all edit boxes.  The
+// One lane per word of the grid (WordGrid, rv_words.h) of the voxel box that bounds all edit boxes.  The
 // lane folds every box, in order, into a set mask and a clear mask (a later box overrides an earlier one
 // bit by bit) and is the word's only writer: no atomics, no two lanes on one word.
 __global__ void __launch_bounds__(256) k_edit_bits(uint32_t* __restrict__ brick, World w,
-                                                   const rv_edit_box* __restrict__ boxes, int nboxes, int wx0, int wy0,
-                                                   int wz0, int nwy, int nwz, uint64_t nwords,
+                                                   const rv_edit_box* __restrict__ boxes, int nboxes, WordGrid grid,
                                                    uint32_t* __restrict__ changed) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nwords) return;
-    const int z = wz0 + (int)(g % (uint64_t)nwz);
-    const uint64_t t = g / (uint64_t)nwz;
-    const int wy = wy0 + (int)(t % (uint64_t)nwy), wx = wx0 + (int)(t / (uint64_t)nwy);
-    const int X0 = wx * 8, Y0 = wy * 4;   // the word's voxels: x X0..X0+7 (bit & 7), y Y0..Y0+3 (bit >> 3)
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= grid.nwords) return;
+    int wx, wy, z;
+    grid.word(g, wx, wy, z);
+    const int X0 = wx * 8, Y0 = wy * 4;
     uint32_t set = 0, clr = 0;
     for (int i = 0; i < nboxes; i++) {
         const rv_edit_box b = boxes[i];
@@ -33,8 +31,7 @@ __global__ void __launch_bounds__(256) k_edit_bits(uint32_t* __restrict__ brick,
         if (b.solid) { set |= m; clr &= ~m; } else { clr |= m; set &= ~m; }
     }
     if ((set | clr) == 0) return;
-    // brick (x >> 3, y >> 3, z >> 3), word (y >> 2 & 1) | (z & 7) << 1 (k_fill_bricks' order)
-    const uint64_t bi = bits_word_index(brick_of(w, wx, wy >> 1, z >> 3), (uint32_t)(wy & 1) | ((uint32_t)(z & 7) << 1));
+    const uint64_t bi = brick_word_index(w, wx, wy, z);
     const uint32_t old = brick[bi];
     const uint32_t nw = (old & ~clr) | set;
     if (nw != old) {
@@ -43,16 +40,11 @@ __global__ void __launch_bounds__(256) k_edit_bits(uint32_t* __restrict__ brick,
     }
 }
 
-// ================================================================ launchers
-static inline uint32_t nblk(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
+// ================================================================ launcher
 void launch_edit_bits(hipStream_t s, uint32_t* brick, const World& w, const rv_edit_box* boxes, int n,
-                      const int lo[3], const int hi[3], uint32_t* changed) {
-    const int wx0 = lo[0] >> 3, wy0 = lo[1] >> 2, wz0 = lo[2];
-    const int nwx = ((hi[0] - 1) >> 3) - wx0 + 1, nwy = ((hi[1] - 1) >> 2) - wy0 + 1, nwz = hi[2] - wz0;
-    const uint64_t nwords = (uint64_t)nwx * (uint64_t)nwy * (uint64_t)nwz;
-    hipLaunchKernelGGL(k_edit_bits, dim3(nblk(nwords)), dim3(256), 0, s, brick, w, boxes, n, wx0, wy0, wz0, nwy, nwz,
-                       nwords, changed);
+                      const rv_voxel_box& box, uint32_t* changed) {
+    const WordGrid grid = word_grid(box);
+    hipLaunchKernelGGL(k_edit_bits, dim3(nblk(grid.nwords)), dim3(256), 0, s, brick, w, boxes, n, grid, changed);
 }
 
 }  // namespace rv

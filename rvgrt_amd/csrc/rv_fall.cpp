@@ -14,34 +14,25 @@ bool args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t max_fall, const
     return detach_args_ok(X, Y, Z, b, 0, comps, cap, nullptr, 0) && max_fall >= 0 && max_fall <= Y;
 }
 
-size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 // The nc components (records and clearances by slot) in ascending order of their seeds: the first
-// min(cap, nc) as rv_fallen, the voxel box of every cleared and every set voxel, and the voxels' sum.
-void write_fallen(const DetachBox& b, const uint32_t* rec, const uint32_t* clearance, uint32_t nc, int32_t max_fall,
-                  rv_fallen* comps, int64_t cap, int lo[3], int hi[3]) {
+// min(cap, nc) as rv_fallen.  Returns the voxel box of every cleared and every set voxel (nc > 0).
+rv_voxel_box write_fallen(const DetachBox& b, const DetachRec* rec, const uint32_t* clearance, uint32_t nc,
+                          int32_t max_fall, rv_fallen* comps, int64_t cap) {
     const std::vector<uint32_t> order = detach_seed_order(rec, nc);
-    for (int a = 0; a < 3; a++) { lo[a] = INT32_MAX; hi[a] = 0; }
+    rv_voxel_box all = empty_box();
     for (uint32_t i = 0; i < nc; i++) {
         const uint32_t sl = order[i];
-        const rv_component k = detach_component(b, rec + (size_t)DETACH_REC * sl);
         const int32_t fall = (int32_t)fall_rows(clearance[sl], max_fall);
-        for (int a = 0; a < 3; a++) {
-            lo[a] = std::min(lo[a], k.lo[a] - (a == 1 ? fall : 0));
-            hi[a] = std::max(hi[a], k.hi[a]);
-        }
+        rv_voxel_box v = detach_rec_box(b, rec[sl]);
+        v.y0 -= fall;
+        box_include(all, v);
         if ((int64_t)i < cap) {
-            comps[i].comp = k;
+            comps[i].comp = detach_component(b, rec[sl]);
             comps[i].fall = fall;
             comps[i].flags = fall_stopped(clearance[sl], max_fall) ? RV_FALL_STOPPED : 0u;
         }
     }
-}
-
-void set_changed(rv_voxel_box* changed, const int lo[3], const int hi[3], bool any) {
-    if (!changed) return;
-    if (any) *changed = rv_voxel_box{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
-    else *changed = rv_voxel_box{0, 0, 0, 0, 0, 0};
+    return all;
 }
 
 }  // namespace
@@ -56,53 +47,39 @@ rv_status rv_world_fall(rv_ctx* c, const rv_voxel_box* box, int32_t max_fall, rv
     if (!c->world_ready) return fail(c, RV_ERR_STATE, "rv_world_fall before a world build or import");
     const DetachBox b = detach_box(*box);
     const DetachLayout l = detach_layout(b);
-    const uint32_t V = b.voxels();
-    // the query's scratch and, behind it, one clearance dword per component: at most ceil(V / 2)
-    if (rv_status s = c->detach_scratch.reserve(c, (l.total + up64((V + 1) / 2)) * 4)) return s;
-    uint32_t* clearance = c->detach_scratch + l.total;
-    if (c->world_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_world, 0));
-    const World w = current_world(c);
-    launch_detach_query(c->stream, w, b, c->detach_scratch);
-    LAUNCH_CHECK(c);
+    // behind the query's scratch, one clearance dword per component: at most ceil(V / 2)
     uint32_t cnt[2] = {0, 0};   // components, detached voxels
-    HIP_TRY(c, hipMemcpyAsync(cnt, c->detach_scratch + l.cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (rv_status s = detach_run_query(c, b, detach_up64((b.voxels() + 1) / 2), cnt)) return s;
+    uint32_t* clearance = c->detach_scratch + l.total;
+    const World w = current_world(c);
     const uint32_t nc = cnt[0];
     if (n_comps) *n_comps = nc;
     if (n_voxels) *n_voxels = cnt[1];
     c->fall_calls++;
-    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    set_changed(changed, lo, hi, false);
+    if (changed) *changed = rv_voxel_box{0, 0, 0, 0, 0, 0};
     rv_status st = RV_OK;
     if (nc) {
         launch_fall_clearance(c->stream, w, b, c->detach_scratch, nc, max_fall, clearance);
         LAUNCH_CHECK(c);
-        c->detach_h.resize((size_t)DETACH_REC * nc);
         c->fall_h.resize(nc);
-        HIP_TRY(c, hipMemcpyAsync(c->detach_h.data(), c->detach_scratch + l.rec, (size_t)DETACH_REC * nc * 4,
-                                  hipMemcpyDeviceToHost, c->stream));
+        if (rv_status s = detach_copy_records(c, b, nc)) return s;
         HIP_TRY(c, hipMemcpyAsync(c->fall_h.data(), clearance, (size_t)nc * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const uint32_t* rec = c->detach_h.data();
-        write_fallen(b, rec, c->fall_h.data(), nc, max_fall, comps, cap, lo, hi);
-        set_changed(changed, lo, hi, true);
+        const DetachRec* rec = c->detach_h.data();
+        const rv_voxel_box all = write_fallen(b, rec, c->fall_h.data(), nc, max_fall, comps, cap);
+        if (changed) *changed = all;
         // what is cleared lies inside B; what is set may lie below it
-        int clo[3], chi[3];
-        for (int a = 0; a < 3; a++) { clo[a] = lo[a]; chi[a] = hi[a]; }
-        clo[1] = INT32_MAX;
-        for (uint32_t i = 0; i < nc; i++) clo[1] = std::min(clo[1], b.y0 + (int)rec[DETACH_REC * i + 2]);
+        rv_voxel_box cleared = empty_box();
+        for (uint32_t i = 0; i < nc; i++) box_include(cleared, detach_rec_box(b, rec[i]));
         if (rv_status ws = wait_all_frames(c)) return ws;
-        launch_detach_clear(c->stream, c->brick, w, b, c->detach_scratch + l.D, clo, chi);
+        launch_detach_clear(c->stream, c->brick, w, b, c->detach_scratch + l.D, cleared);
         launch_fall_stamp(c->stream, c->brick, w, b, c->detach_scratch, max_fall, clearance);
         LAUNCH_CHECK(c);
-        for (uint32_t i = 0; i < nc; i++) {   // x and z do not change in a fall
-            const uint32_t* r = rec + (size_t)DETACH_REC * i;
-            persist_mark(c, ColumnRange{(b.x0 + (int)r[1]) >> 3, ((b.x0 + (int)r[4]) >> 3) + 1, (b.z0 + (int)r[3]) >> 3,
-                                        ((b.z0 + (int)r[6]) >> 3) + 1});
-        }
+        for (uint32_t i = 0; i < nc; i++)   // x and z do not change in a fall
+            persist_mark(c, columns_under(detach_rec_box(b, rec[i])));
         c->fall_comps += nc;
         c->fall_voxels += cnt[1];
-        st = edit_finish(c, lo, hi);   // waits for the clear and the stamp as well
+        st = edit_finish(c, all);   // waits for the clear and the stamp as well
     }
     c->detach_scratch.trim(EDIT_SCRATCH_KEEP);
     return st;
@@ -119,7 +96,7 @@ rv_status rv_world_fall_info(rv_ctx* c, uint64_t* calls, uint64_t* components_mo
 rv_status rv_world_fall_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, const uint32_t* bits, const rv_voxel_box* box,
                            int32_t max_fall, rv_fallen* comps, int64_t cap, int64_t* n_comps, uint64_t* n_voxels,
                            rv_voxel_box* changed, uint32_t* bits_out, size_t bits_bytes) {
-    if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !bits) return RV_ERR_INVALID;
+    if (!linear_dims_ok(log2_x, log2_y, log2_z) || !bits) return RV_ERR_INVALID;
     if (!args_ok(1 << log2_x, 1 << log2_y, 1 << log2_z, box, max_fall, comps, cap)) return RV_ERR_INVALID;
     const size_t world_bytes = ((size_t)1 << (log2_x + log2_y + log2_z)) / 8;
     if (bits_out && bits_bytes < world_bytes) return RV_ERR_INVALID;
@@ -127,7 +104,7 @@ rv_status rv_world_fall_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, const
     const DetachBox b = detach_box(*box);
     DetachHost q;
     detach_host_query(w, b, nullptr, q);
-    const uint32_t nc = (uint32_t)(q.rec.size() / DETACH_REC), NW = b.words();
+    const uint32_t nc = (uint32_t)q.rec.size(), NW = b.words();
     // the clearance kernel's scan, word after word and run after run
     std::vector<uint32_t> clearance(nc, FALL_NONE);
     const uint32_t limit = fall_scan_limit(max_fall);
@@ -141,9 +118,8 @@ rv_status rv_world_fall_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, const
             *best = std::min(*best, v);
         }
     }
-    int lo[3], hi[3];
-    write_fallen(b, q.rec.data(), clearance.data(), nc, max_fall, comps, cap, lo, hi);
-    set_changed(changed, lo, hi, nc > 0);
+    const rv_voxel_box all = write_fallen(b, q.rec.data(), clearance.data(), nc, max_fall, comps, cap);
+    if (changed) *changed = nc ? all : rv_voxel_box{0, 0, 0, 0, 0, 0};
     if (n_comps) *n_comps = nc;
     if (n_voxels) *n_voxels = q.voxels;
     if (!bits_out) return RV_OK;

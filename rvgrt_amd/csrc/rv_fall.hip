@@ -7,11 +7,6 @@
 
 namespace rv {
 
-__device__ __forceinline__ uint32_t fall_wave_umin(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = umin(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-
 // ================================================================ the clearance
 // Every run of D reports its constraint to its component's dword by a relaxed agent-scope atomic min; the
 // lanes of a wave that hold runs of one component reduce first (the leader loop of k_detach_stats), so a
@@ -43,7 +38,7 @@ __global__ void __launch_bounds__(256) k_fall_clearance(World w, DetachBox b, ui
             uint32_t least = v;
             bool writer = mine;
             if (__popcll(same) > 1) {   // wave-uniform
-                least = fall_wave_umin(mine ? v : FALL_NONE);
+                least = wave_umin(mine ? v : FALL_NONE);
                 writer = lane == (uint32_t)src;
             }
             if (writer) __hip_atomic_fetch_min(clearance + ss, least, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -73,19 +68,17 @@ __global__ void __launch_bounds__(256) k_fall_stamp(uint32_t* brick, World w, De
         const int y = b.y0 + d.yl - (int)fall_rows(clearance[slot[r - 1u]], max_fall);
         if (y < 0 || y >= w.Y) continue;   // never: clearance stops at the floor
         const uint64_t bits = (uint64_t)(detach_low_bits(len) << s) << (xs & 7);
-        const uint32_t wd = ((uint32_t)(y >> 2) & 1u) | ((uint32_t)(z & 7) << 1), sh = 8u * ((uint32_t)y & 3u);
+        const uint32_t sh = 8u * ((uint32_t)y & 3u);
         for (int k = 0; k < 5; k++) {
             const uint32_t byte = (uint32_t)(bits >> (8 * k)) & 0xFFu;
             const int bx = (xs >> 3) + k;
             if (!byte || bx * 8 >= w.X) continue;
-            atomicOr(brick + bits_word_index(brick_of(w, bx, y >> 3, z >> 3), wd), byte << sh);
+            atomicOr(brick + brick_word_index(w, bx, y >> 2, z), byte << sh);
         }
     }
 }
 
 // ================================================================ launchers
-static inline uint32_t nblk(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 void launch_fall_clearance(hipStream_t s, const World& w, const DetachBox& b, const uint32_t* scratch, uint32_t nc,
                            int32_t max_fall, uint32_t* clearance) {
     const DetachLayout l = detach_layout(b);

@@ -351,7 +351,7 @@ struct rv_ctx {
     // detach_layout, freed after a call when above the edit scratch's keep limit), the host copy of the
     // component records and rv_world_detached_info's sums
     DevBuf<uint32_t> detach_scratch;
-    std::vector<uint32_t> detach_h;
+    std::vector<DetachRec> detach_h;
     uint64_t detach_calls = 0, detach_scanned = 0, detach_cleared = 0;
     // rv_world_fall (rv_fall.cpp): it works in detach_scratch, its clearances behind the query's layout; the
     // host copy of the clearances and rv_world_fall_info's sums
@@ -551,6 +551,14 @@ RV_HIDDEN rv_status tile_list(rv_ctx* c, const int32_t* tile_ids, int32_t ntiles
 // rv_edit.cpp: rv_create's limits on the world dims; a box list's validity in such a world
 RV_HIDDEN bool dims_ok(int lx, int ly, int lz);
 RV_HIDDEN bool boxes_ok(int lx, int ly, int lz, const rv_edit_box* b, int n);
+// the dims of the host-only forms that take RV_WORLD_BITS words: a word is 32 x-consecutive voxels of one row
+inline bool linear_dims_ok(int lx, int ly, int lz) { return dims_ok(lx, ly, lz) && lx >= 5; }
+// rv_voxel_box is the host's voxel box [lo, hi) (its union, WordGrid and ColumnRange: include/rvgrt/rv_words.h).
+// voxel_box_ok: inside a window of X Y Z voxels and non-empty
+inline bool voxel_box_ok(int X, int Y, int Z, const rv_voxel_box& b) {
+    return b.x0 >= 0 && b.y0 >= 0 && b.z0 >= 0 && b.x1 <= X && b.y1 <= Y && b.z1 <= Z && b.x1 > b.x0 && b.y1 > b.y0 &&
+           b.z1 > b.z0;
+}
 // The nested boxes of a local CSDF rebuild (launch_csdf_box) around the coarse cells E = [e0, e1) whose
 // solidity may have changed, in a grid of S cells: rf = E grown by 64 per axis, and the inputs it needs
 // read backwards through the passes (rv_edit.cpp), each clipped to the grid; passes() = the cells the four
@@ -565,30 +573,36 @@ constexpr size_t EDIT_SCRATCH_KEEP = (size_t)64 << 20;
 // the passes over `n` sets of boxes, one after the other, through edit_t0 / edit_t1; waits for them, then
 // frees the scratch when it is above EDIT_SCRATCH_KEEP
 RV_HIDDEN rv_status csdf_rebuild_boxes(rv_ctx* c, const CsdfBoxes* b, int n);
-// The end of an edit whose changed voxels lie in the voxel box [lo, hi), after the caller has waited for the
+// The end of an edit whose changed voxels lie in the voxel box `changed`, after the caller has waited for the
 // frames, written the bits and marked the columns: geom_ver, the exits (world_top), the local CSDF rebuild
 // and mark_world or the whole-grid build, whichever visits fewer cells, and rv_world_edit_info's record
-RV_HIDDEN rv_status edit_finish(rv_ctx* c, const int lo[3], const int hi[3]);
+RV_HIDDEN rv_status edit_finish(rv_ctx* c, const rv_voxel_box& changed);
 
 // rv_detached.cpp: what rv_world_fall shares with rv_world_detached -- the check of the box, flags, cap and
 // arrays; the slots of nc component records in ascending order of their seeds and one record as rv_component
-// in window coordinates; and the host form of the query: the kernels' passes word after word, which leave what
-// launch_detach_query leaves on the device (include/rvgrt/rv_detached.h)
+// in window coordinates; the host form of the query: the kernels' passes word after word, which leave what
+// launch_detach_query leaves on the device (include/rvgrt/rv_detached.h); and the device form's opening.
 namespace rv { struct DetachBox; }
 struct DetachHost {
-    std::vector<uint32_t> W, D, L, slot, rec;
+    std::vector<uint32_t> W, D, L, slot;
+    std::vector<DetachRec> rec;
     uint64_t voxels = 0;   // detached
 };
 RV_HIDDEN bool detach_args_ok(int X, int Y, int Z, const rv_voxel_box* b, int32_t flags, const void* comps, int64_t cap,
                               const uint32_t* mask, size_t mask_bytes);
-RV_HIDDEN std::vector<uint32_t> detach_seed_order(const uint32_t* rec, uint32_t nc);
-RV_HIDDEN rv_component detach_component(const rv::DetachBox& b, const uint32_t* r);
+RV_HIDDEN std::vector<uint32_t> detach_seed_order(const DetachRec* rec, uint32_t nc);
+RV_HIDDEN rv_component detach_component(const rv::DetachBox& b, const DetachRec& r);
 RV_HIDDEN void detach_host_query(const LinearWorld& w, const rv::DetachBox& b, uint32_t* mask, DetachHost& q);
+// detach_run_query: detach_scratch reserved (the query's layout + extra_dwords), the wait for a world write on
+// another stream, the query's launches, cnt = {components, detached voxels} read back (waits for the stream).
+// detach_copy_records: the copy of nc records into detach_h enqueued; the caller adds its own and waits once.
+RV_HIDDEN rv_status detach_run_query(rv_ctx* c, const rv::DetachBox& b, size_t extra_dwords, uint32_t cnt[2]);
+RV_HIDDEN rv_status detach_copy_records(rv_ctx* c, const rv::DetachBox& b, uint32_t nc);
 
 // rv_persist.cpp: the marking, capturing and restoring that rv_world_edit, rv_world_import, rv_world_build
 // and rv_world_scroll do while persistence is on (every one returns at once while it is off).  A range is
-// the brick columns [bx0, bx1) x [bz0, bz1) of the window; keys are taken at the origin (ox, oz).
-struct ColumnRange { int bx0, bx1, bz0, bz1; };
+// the brick columns [bx0, bx1) x [bz0, bz1) of the window (ColumnRange, rv_words.h); keys are taken at the origin
+// (ox, oz).
 RV_HIDDEN void persist_mark(rv_ctx* c, const ColumnRange& r);
 // how many columns of r are dirty / have an entry in the store when the window's origin is (ox, oz)
 RV_HIDDEN size_t persist_dirty_in(const rv_ctx* c, const ColumnRange& r, int32_t ox, int32_t oz);

@@ -125,8 +125,6 @@ __global__ void __launch_bounds__(256) k_tex_box(uint32_t* __restrict__ tex, Wor
 }
 
 // ================================================================ launchers
-static inline uint32_t nblk(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 void launch_scroll_bricks(hipStream_t s, uint32_t* brick, const World& w, int axis, int nb, void* scratch) {
     const uint64_t NBX = (uint64_t)w.X >> 3, NBY = (uint64_t)w.Y >> 3, NBZ = (uint64_t)w.Z >> 3;
     const uint64_t a = (uint64_t)(nb < 0 ? -nb : nb);   // bricks the window moves by; a < the axis' bricks

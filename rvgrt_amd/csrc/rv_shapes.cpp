@@ -26,7 +26,6 @@ rv_status rv_world_edit_shapes(rv_ctx* c, const rv_edit_shape* shapes, int32_t n
         c->edit_full = 0;
         return RV_OK;
     }
-    const int lo[3] = {u.x0, u.y0, u.z0}, hi[3] = {u.x1, u.y1, u.z1};
     if (rv_status ws = wait_all_frames(c)) return ws;
 
     // the bits: shapes to the device, one lane per word of the union box
@@ -35,7 +34,7 @@ rv_status rv_world_edit_shapes(rv_ctx* c, const rv_edit_shape* shapes, int32_t n
     HIP_TRY(c, hipMemcpyAsync(c->shape_list, c->shape_h.data(), (size_t)n * sizeof(rv_edit_shape), hipMemcpyHostToDevice,
                               c->stream));
     HIP_TRY(c, hipMemsetAsync(c->shape_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    launch_edit_shapes(c->stream, c->brick, current_world(c), c->shape_list, n, lo, hi, c->shape_counts);
+    launch_edit_shapes(c->stream, c->brick, current_world(c), c->shape_list, n, u, c->shape_counts);
     LAUNCH_CHECK(c);
     unsigned long long cnt[2] = {0, 0};   // turned on, turned off
     HIP_TRY(c, hipMemcpyAsync(cnt, c->shape_counts, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
@@ -48,21 +47,21 @@ rv_status rv_world_edit_shapes(rv_ctx* c, const rv_edit_shape* shapes, int32_t n
 
     for (int i = 0; i < n; i++) {   // persistence: the columns under each non-empty clipped box
         const rv_voxel_box& b = c->shape_box_h[(size_t)i];
-        if (b.x1 > b.x0) persist_mark(c, ColumnRange{b.x0 >> 3, ((b.x1 - 1) >> 3) + 1, b.z0 >> 3, ((b.z1 - 1) >> 3) + 1});
+        if (b.x1 > b.x0) persist_mark(c, columns_under(b));
     }
-    return edit_finish(c, lo, hi);
+    return edit_finish(c, u);
 }
 
 rv_status rv_world_edit_shapes_at(int32_t log2_x, int32_t log2_y, int32_t log2_z, uint32_t* bits,
                                   const rv_edit_shape* shapes, int32_t n, uint64_t* n_set, uint64_t* n_cleared) {
-    if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !bits || !shapes_ok(shapes, n)) return RV_ERR_INVALID;
+    if (!linear_dims_ok(log2_x, log2_y, log2_z) || !bits || !shapes_ok(shapes, n)) return RV_ERR_INVALID;
     shapes_apply_linear(log2_x, log2_y, log2_z, bits, shapes, n, n_set, n_cleared);
     return RV_OK;
 }
 
 rv_status rv_world_edit_shapes_box(int32_t log2_x, int32_t log2_y, int32_t log2_z, const rv_edit_shape* shapes,
                                    int32_t n, rv_voxel_box* each, rv_voxel_box* all) {
-    if (!dims_ok(log2_x, log2_y, log2_z) || log2_x < 5 || !all || !shapes_ok(shapes, n)) return RV_ERR_INVALID;
+    if (!linear_dims_ok(log2_x, log2_y, log2_z) || !all || !shapes_ok(shapes, n)) return RV_ERR_INVALID;
     shapes_boxes(log2_x, log2_y, log2_z, shapes, n, each, all);
     return RV_OK;
 }

@@ -6,9 +6,9 @@
 
 namespace rv {
 
-// k_edit_bits' scheme (rv_edit.hip): one lane per 32-bit brick word (8 x, 4 y, 1 z voxels) of the voxel box
-// that bounds all clipped shape boxes.  The lane folds every shape, in order, into a set mask and a clear mask
-// (a later shape overrides an earlier one bit by bit) and is the word's only writer.
+// One lane per word of the grid (WordGrid, rv_words.h) of the voxel box that bounds all clipped shape boxes.
+// The lane folds every shape, in order, into a set mask and a clear mask (a later shape overrides an earlier
+// one bit by bit) and is the word's only writer.
 //   - The shape list is the same for every lane and the loop index is wave-uniform, so a shape, its clipped
 //     box and its q products live in SGPRs (scalar loads, scalar multiplies).
 //   - A word outside a shape's clipped box skips the shape on integer compares, before any 64-bit multiply.
@@ -19,17 +19,15 @@ namespace rv {
 //     (pre-zeroed).  Integer sums do not depend on the order.
 // Every word lies inside the window (X a multiple of 8, Y of 4), so the window's clip needs no mask.
 __global__ void __launch_bounds__(256) k_edit_shapes(uint32_t* __restrict__ brick, World w,
-                                                     const rv_edit_shape* __restrict__ shapes, int nshapes, int wx0,
-                                                     int wy0, int wz0, int nwy, int nwz, uint64_t nwords,
-                                                     unsigned long long* __restrict__ counts) {
+                                                     const rv_edit_shape* __restrict__ shapes, int nshapes,
+                                                     WordGridT<uint64_t> grid, unsigned long long* __restrict__ counts) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = g < nwords;   // no early return: the wave reduction below needs every lane
+    const bool live = g < grid.nwords;   // no early return: the wave reduction below needs every lane
     uint32_t on = 0, off = 0;
     if (live) {
-        const int z = wz0 + (int)(g % (uint64_t)nwz);
-        const uint64_t t = g / (uint64_t)nwz;
-        const int wy = wy0 + (int)(t % (uint64_t)nwy), wx = wx0 + (int)(t / (uint64_t)nwy);
-        const int X0 = wx * 8, Y0 = wy * 4;   // the word's voxels: x X0..X0+7 (bit & 7), y Y0..Y0+3 (bit >> 3)
+        int wx, wy, z;
+        grid.word(g, wx, wy, z);
+        const int X0 = wx * 8, Y0 = wy * 4;
         const int32_t D[3] = {w.X, w.Y, w.Z};
         uint32_t set = 0, clr = 0;
         for (int i = 0; i < nshapes; i++) {
@@ -50,9 +48,7 @@ __global__ void __launch_bounds__(256) k_edit_shapes(uint32_t* __restrict__ bric
             if (s.solid) { set |= m; clr &= ~m; } else { clr |= m; set &= ~m; }
         }
         if (set | clr) {
-            // brick (x >> 3, y >> 3, z >> 3), word (y >> 2 & 1) | (z & 7) << 1 (k_fill_bricks' order)
-            const uint64_t bi =
-                bits_word_index(brick_of(w, wx, wy >> 1, z >> 3), (uint32_t)(wy & 1) | ((uint32_t)(z & 7) << 1));
+            const uint64_t bi = brick_word_index(w, wx, wy, z);
             const uint32_t old = brick[bi];
             const uint32_t nw = (old & ~clr) | set;
             if (nw != old) {
@@ -74,12 +70,9 @@ __global__ void __launch_bounds__(256) k_edit_shapes(uint32_t* __restrict__ bric
 }
 
 void launch_edit_shapes(hipStream_t s, uint32_t* brick, const World& w, const rv_edit_shape* shapes, int n,
-                        const int lo[3], const int hi[3], unsigned long long* counts) {
-    const int wx0 = lo[0] >> 3, wy0 = lo[1] >> 2, wz0 = lo[2];
-    const int nwx = ((hi[0] - 1) >> 3) - wx0 + 1, nwy = ((hi[1] - 1) >> 2) - wy0 + 1, nwz = hi[2] - wz0;
-    const uint64_t nwords = (uint64_t)nwx * (uint64_t)nwy * (uint64_t)nwz;
-    hipLaunchKernelGGL(k_edit_shapes, dim3((uint32_t)((nwords + 255) / 256)), dim3(256), 0, s, brick, w, shapes, n, wx0,
-                       wy0, wz0, nwy, nwz, nwords, counts);
+                        const rv_voxel_box& box, unsigned long long* counts) {
+    const WordGridT<uint64_t> grid = word_grid<uint64_t>(box);
+    hipLaunchKernelGGL(k_edit_shapes, dim3(nblk(grid.nwords)), dim3(256), 0, s, brick, w, shapes, n, grid, counts);
 }
 
 }  // namespace rv

@@ -3,11 +3,16 @@
 // coordinates), rows and words at the far corner of the bit array, and a few hundred random lists, each checked
 // voxel by voxel against the definition written out with 128-bit integers.  The bit array is a heap block of
 // exactly the world's size, so a word written past either end is a report.  Exit status 0: all agreed.
+//
+// And what the in-place voxel writes share (include/rvgrt/rv_words.h): the word grid of a voxel box against a
+// brute-force scan of the box's voxels, the brick columns under a box, and a component record's box.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../../include/rvgrt/rv_shapes.h"
+#include "../../include/rvgrt/rv_words.h"
 
 using namespace rv;
 
@@ -79,7 +84,87 @@ static rv_edit_shape shape(int kind, int solid, int cx, int cy, int cz, int rx, 
     return rv_edit_shape{kind, solid, {cx, cy, cz}, {rx, ry, rz}};
 }
 
+// The word grid and the columns of one box in a window of X Y Z voxels: the words enumerated by g in
+// [0, nwords) are pairwise distinct, lie inside the window, and are exactly the words that hold a voxel of the
+// box (the words of its word-aligned hull); both index widths enumerate the same words; the columns are the
+// ones the box's voxels stand on.
+static void check_box(int X, int Y, int Z, const rv_voxel_box& b) {
+    const WordGrid g = word_grid(b);
+    const WordGridT<uint64_t> g64 = word_grid<uint64_t>(b);
+    const int NWX = X / 8, NWY = Y / 4, NBX = X / 8, NBZ = Z / 8;
+    std::vector<uint8_t> want((size_t)NWX * NWY * Z, 0), got(want.size(), 0), cols((size_t)NBX * NBZ, 0), rc(cols.size(), 0);
+    size_t nwant = 0;
+    for (int z = b.z0; z < b.z1; z++)
+        for (int y = b.y0; y < b.y1; y++)
+            for (int x = b.x0; x < b.x1; x++) {
+                uint8_t& m = want[(size_t)(x >> 3) + (size_t)NWX * ((size_t)(y >> 2) + (size_t)NWY * (size_t)z)];
+                nwant += !m;
+                m = 1;
+                cols[(size_t)(x >> 3) + (size_t)NBX * (size_t)(z >> 3)] = 1;
+            }
+    bool ok = g64.nwords == g.nwords && g64.nwords <= WORD_GRID_MAX && g.nwords == nwant;
+    for (uint32_t i = 0; ok && i < g.nwords; i++) {
+        int wx, wy, z, wx2, wy2, z2;
+        g.word(i, wx, wy, z);
+        g64.word(i, wx2, wy2, z2);
+        ok = wx == wx2 && wy == wy2 && z == z2 && wx >= 0 && wy >= 0 && z >= 0 && wx < NWX && wy < NWY && z < Z;
+        if (!ok) break;
+        uint8_t& m = got[(size_t)wx + (size_t)NWX * ((size_t)wy + (size_t)NWY * (size_t)z)];
+        ok = !m;   // pairwise distinct
+        m = 1;
+    }
+    ok = ok && got == want;
+    const ColumnRange r = columns_under(b);
+    for (int bz = r.bz0; bz < r.bz1; bz++)
+        for (int bx = r.bx0; bx < r.bx1; bx++) {
+            if (bx < 0 || bx >= NBX || bz < 0 || bz >= NBZ) { ok = false; continue; }
+            rc[(size_t)bx + (size_t)NBX * (size_t)bz] = 1;
+        }
+    ok = ok && rc == cols;
+    if (!ok) {
+        std::printf("word grid / columns of box %d %d %d .. %d %d %d in %d %d %d\n", b.x0, b.y0, b.z0, b.x1, b.y1, b.z1, X, Y, Z);
+        failures++;
+    }
+}
+
+// Boxes whose x0 and x1 - 1 take the residues {0, 1, 7} mod 8 and whose y0 and y1 - 1 the residues {0, 3} mod 4,
+// in the first and the last brick of the axis (both window faces), over a few z ranges; 200 random boxes; and
+// component records against the boxes they were built from.
+static void check_words(int X, int Y, int Z) {
+    std::vector<int> xs, ys;
+    for (int base : {0, X - 8})
+        for (int r : {0, 1, 7}) xs.push_back(base + r);
+    for (int base : {0, Y - 4})
+        for (int r : {0, 3}) ys.push_back(base + r);
+    const int zs[4][2] = {{0, 1}, {Z - 1, Z}, {7, 9}, {0, Z}};
+    for (int x0 : xs) for (int xl : xs) for (int y0 : ys) for (int yl : ys) for (const int* z : zs)
+        if (xl >= x0 && yl >= y0) check_box(X, Y, Z, rv_voxel_box{x0, y0, z[0], xl + 1, yl + 1, z[1]});
+    for (int t = 0; t < 200; t++) {
+        const int x0 = rnd_in(0, X - 1), y0 = rnd_in(0, Y - 1), z0 = rnd_in(0, Z - 1);
+        const rv_voxel_box b{x0, y0, z0, rnd_in(x0 + 1, X), rnd_in(y0 + 1, Y), rnd_in(z0 + 1, Z)};
+        check_box(X, Y, Z, b);
+        // a record of the query box b: inclusive box-local bounds lo <= hi
+        DetachRec rec{};
+        const int n[3] = {b.x1 - b.x0, b.y1 - b.y0, b.z1 - b.z0};
+        for (int a = 0; a < 3; a++) { rec.lo[a] = (uint32_t)rnd_in(0, n[a] - 1); rec.hi[a] = (uint32_t)rnd_in((int)rec.lo[a], n[a] - 1); }
+        const rv_voxel_box v = detach_rec_box(b, rec);
+        const int o[3] = {b.x0, b.y0, b.z0}, vlo[3] = {v.x0, v.y0, v.z0}, vhi[3] = {v.x1, v.y1, v.z1};
+        for (int a = 0; a < 3; a++)
+            if (vlo[a] != o[a] + (int)rec.lo[a] || vhi[a] != o[a] + (int)rec.hi[a] + 1) { std::printf("detach_rec_box\n"); failures++; break; }
+    }
+    // the record is the eight dwords the kernels write by index: voxels, min x y z, max x y z, seed
+    const uint32_t raw[DETACH_REC] = {10, 1, 2, 3, 4, 5, 6, 7};
+    DetachRec rec;
+    std::memcpy(&rec, raw, sizeof(rec));
+    if (rec.voxels != 10 || rec.lo[0] != 1 || rec.lo[2] != 3 || rec.hi[0] != 4 || rec.hi[2] != 6 || rec.seed != 7) {
+        std::printf("DetachRec field order\n");
+        failures++;
+    }
+}
+
 int main() {
+    check_words(32, 16, 16);
+    check_words(64, 32, 16);
     const int R = RV_SHAPE_MAX_R2, CMAX = SHAPE_MAX_C2;
     // extremes: the largest radii around the centre, thin slabs at an odd and an even centre, every kind
     for (int kind = 0; kind < 4; kind++) {

@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import random_rays
-from gpu_world import (block_in_view, draw, edited, run_ranks, rv, same_frames, same_world, sparse_bits,
+from gpu_world import (block_in_view, draw, edited, pack, run_ranks, rv, same_frames, same_world, sparse_bits,
                        twin_edit, voxels)
+import np_shapes as S
 
 pytestmark = pytest.mark.gpu
 
@@ -194,7 +195,75 @@ def test_frames_across_an_edit(rv, atlas, mode, in_flight):
     t.close()
 
 
-# ---------------------------------------------------------------- 5. status behaviour
+# ---------------------------------------------------------------- 5. the word grid's edges
+def _edge_spans(n, m):
+    """(first, last) voxel pairs of an axis of n voxels whose ends take the residues that matter mod m (8 along
+    x: 0, 1, 7; 4 along y: 0, 3) in the first and the last word of the axis."""
+    return [(0, 0), (1, m - 1), (m - 1, m), (0, n - 1), (n - m, n - m + 1), (n - m + 1, n - 1), (n - 1, n - 1),
+            (1, n - m), (m - 1, m - 1), (m, n - 2)]
+
+
+@pytest.mark.parametrize("lg", [(5, 4, 4), (6, 5, 4)])
+def test_word_grid_edges_of_the_three_writers(rv, lg):
+    """The three kernels that run one lane per brick word of a voxel box (box edit, shape edit, detached clear)
+    in the smallest windows where a wrong row or slice stride of the word grid, or a wrong half-brick (wy >> 1),
+    shows: 32 x 16 x 16 and 64 x 32 x 16 voxels -- a 16-voxel axis is two bricks and four word rows.  Boxes and
+    shapes start and end on every residue of a word along x and y at both window faces; each result is compared
+    exactly with the host: edited(), np_shapes.apply, and rv_world_detached_at plus a clear of its mask."""
+    X, Y, Z = (1 << l for l in lg)
+    E = S.ELLIPSOID
+    r, t = (rv.StateRender(lg, 64, 64) for _ in range(2))
+    vox = np.random.default_rng(5 + lg[0]).random((Z, Y, X)) < 0.5
+    r.world_import(rv.RV_WORLD_BITS, pack(vox))
+    r.csdf_build()
+    # 1. boxes: every x span with every y span, over one slice, a brick seam or all of z; later ones win
+    xs, ys = _edge_spans(X, 8), _edge_spans(Y, 4)
+    zs = [(0, 0), (Z - 1, Z - 1), (7, 8), (0, Z - 1)]
+    boxes = [(xa, ya, zs[(i + j) % 4][0], xb + 1, yb + 1, zs[(i + j) % 4][1] + 1, (i + j) & 1)
+             for i, (xa, xb) in enumerate(xs) for j, (ya, yb) in enumerate(ys)]
+    boxes += [(7, Y - 1, Z - 1, 9, Y, Z, 0), (X - 1, Y - 1, Z - 1, X, Y, Z, int(not vox[Z - 1, Y - 1, X - 1]))]
+    assert all(0 <= b[0] < b[3] <= X and 0 <= b[1] < b[4] <= Y for b in boxes)
+    r.world_edit(boxes)
+    bits = edited(pack(vox), lg, boxes)
+    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), bits), "boxes"
+    assert r.world_edit_info()[0] == 1
+    # 2. shapes: a one-voxel and a radius-2 ellipsoid around both ends of every span, alternately set and cleared
+    vox = voxels(bits, lg)
+    at = [(x, y, z) for (xa, xb), (ya, yb), (za, zb) in zip(xs, ys, zs * 3) for x, y, z in ((xa, ya, za), (xb, yb, zb))]
+    at += [(X - 1, Y - 1, Z - 1), (7, Y - 1, Z - 1), (8, 0, 0)]
+    shapes = [(E, (i + k) & 1, (2 * x + 1, 2 * y + 1, 2 * z + 1), (r2,) * 3)
+              for i, (x, y, z) in enumerate(at) for k, r2 in enumerate((4, 1))]
+    want = S.apply(vox, shapes)
+    assert r.world_edit_shapes(shapes) == want[1:] and want[1] > 0 and want[2] > 0
+    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), pack(want[0])), "shapes"
+    # 3. the clear: a floor, and above it voxel pairs that nothing holds -- across the word seam x = 7 | 8 in the
+    # top corner of the window, across the word-row seam y = 3 | 4, across the brick seam z = 7 | 8
+    vox = np.zeros((Z, Y, X), bool)
+    vox[:, 0, :] = True
+    vox[Z - 2, Y - 1, 7:9] = True
+    vox[5, 3:5, 1] = True
+    vox[7:9, Y - 4, X - 2] = True
+    box = (0, 1, 0, X, Y, Z)
+    r.world_import(rv.RV_WORLD_BITS, pack(vox))
+    r.csdf_build()
+    comps, n, v, mask = rv.detached_at(lg, pack(vox), box)
+    assert (n, v) == (3, 6)
+    got = r.world_detached(box, 1)
+    assert got[1:3] == (n, v) and np.array_equal(got[3], mask)
+    for f in ("seed", "lo", "hi", "voxels"):
+        assert np.array_equal(got[0][f], comps[f]), f
+    det = np.unpackbits(mask.view(np.uint8), bitorder="little")[:X * (Y - 1) * Z].reshape(Z, Y - 1, X).astype(bool)
+    assert det.sum() == 6
+    vox[:, 1:, :] &= ~det
+    assert np.array_equal(r.world_export(rv.RV_WORLD_BITS), pack(vox)), "clear"
+    t.world_import(rv.RV_WORLD_BITS, pack(vox))
+    t.csdf_build()
+    same_world(rv, r, t, "after the clear")
+    r.close()
+    t.close()
+
+
+# ---------------------------------------------------------------- 6. status behaviour
 def test_edit_status_behaviour(rv):
     lg = (7, 6, 7)
     X, Y, Z = 128, 64, 128
@@ -223,7 +292,7 @@ def test_edit_status_behaviour(rv):
     r.close()
 
 
-# ---------------------------------------------------------------- 6. two-rank loopback
+# ---------------------------------------------------------------- 7. two-rank loopback
 def test_two_rank_loop_with_an_edit_equals_one_rank(rv, atlas):
     """Both ranks of a tile-sharded loop apply the same edit between two calls: the gathered frame and
     every rank's GI grid equal one context rendering whole frames one at a time with the same edit."""

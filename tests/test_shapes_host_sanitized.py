@@ -1,7 +1,9 @@
 """The host evaluation of rv_world_edit_shapes (include/rvgrt/rv_shapes.h) under AddressSanitizer and
 UndefinedBehaviorSanitizer: tests/host_shapes builds a stand-alone program with the sanitizer runtimes linked in
 statically -- the test puts nothing into the environment but the two option strings -- that runs the extremes of the arithmetic, the far corner of the bit array and a few
-hundred random lists against the definition, every report fatal.  A CPU test."""
+hundred random lists against the definition, every report fatal.  The same program checks what the in-place
+voxel writes share (include/rvgrt/rv_words.h): the word grid and the brick columns of a voxel box against a scan
+of its voxels, and a component record's box.  A CPU test."""
 import os
 import subprocess
 
