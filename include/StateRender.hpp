@@ -88,6 +88,41 @@ public:
     void editShapes(const rv_edit_shape* shapes, int n, uint64_t* set = nullptr, uint64_t* cleared = nullptr) {
         check(rv_world_edit_shapes(ctx_, shapes, n, set, cleared), ctx_, "rv_world_edit_shapes");
     }
+    // Prefabs kept on the device: an nx x ny x nz block of bits (rows along x padded to 32-bit words) becomes a
+    // pattern, as does a voxel box of the world without leaving the device; the id is the lowest free slot
+    // (rv_pattern_create, rv_pattern_capture, rv_pattern_read, rv_pattern_destroy)
+    int patternCreate(int nx, int ny, int nz, const uint32_t* bits, size_t bytes) {
+        int32_t id = -1;
+        check(rv_pattern_create(ctx_, nx, ny, nz, bits, bytes, &id), ctx_, "rv_pattern_create");
+        return id;
+    }
+    int patternCapture(const rv_voxel_box& box) {
+        int32_t id = -1;
+        check(rv_pattern_capture(ctx_, &box, &id), ctx_, "rv_pattern_capture");
+        return id;
+    }
+    void patternRead(int id, int32_t dims[3], uint32_t* bits = nullptr, size_t bytes = 0) {
+        check(rv_pattern_read(ctx_, id, dims, bits, bytes), ctx_, "rv_pattern_read");
+    }
+    void patternDestroy(int id) { check(rv_pattern_destroy(ctx_, id), ctx_, "rv_pattern_destroy"); }
+    // Patterns pasted into the world by one launch, in order, each at an offset, in one of the 8 orientations that
+    // keep y up, setting, clearing or copying, clipped to the window; the voxels that turned solid / empty into
+    // *set / *cleared, the union of the clipped boxes into *changed (rv_world_stamp)
+    void stampWorld(const rv_stamp* stamps, int n, uint64_t* set = nullptr, uint64_t* cleared = nullptr,
+                    rv_voxel_box* changed = nullptr) {
+        check(rv_world_stamp(ctx_, stamps, n, set, cleared, changed), ctx_, "rv_world_stamp");
+    }
+    // Matter moved by (dx, dy, dz), composed of the calls above: the box captured, cleared where it was and copied
+    // to where it goes in one stampWorld; the horizontal counterpart of fallDetached
+    void moveWorld(const rv_voxel_box& box, int dx, int dy, int dz, uint64_t* set = nullptr, uint64_t* cleared = nullptr,
+                   rv_voxel_box* changed = nullptr) {
+        const int id = patternCapture(box);
+        const rv_stamp s[2] = {{id, RV_STAMP_CLEAR, 0, {box.x0, box.y0, box.z0}},
+                               {id, RV_STAMP_COPY, 0, {box.x0 + dx, box.y0 + dy, box.z0 + dz}}};
+        const rv_status st = rv_world_stamp(ctx_, s, 2, set, cleared, changed);
+        rv_pattern_destroy(ctx_, id);
+        check(st, ctx_, "rv_world_stamp");
+    }
     // What an edit left floating in a voxel box: up to cap components into comps, their total returned; with
     // RV_DETACHED_CLEAR they are cleared like an editWorld of those voxels (rv_world_detached)
     int64_t findDetached(const rv_voxel_box& box, int flags, rv_component* comps, int64_t cap, uint64_t* voxels = nullptr) {

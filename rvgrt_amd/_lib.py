@@ -124,6 +124,22 @@ class rv_fallen(C.Structure):
 # rv_fallen.flags
 RV_FALL_STOPPED = 1
 
+
+class rv_stamp(C.Structure):
+    _fields_ = [("pattern", C.c_int32), ("op", C.c_int32), ("orient", C.c_int32), ("at", C.c_int32 * 3)]
+
+
+class rv_pattern_host(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("bits", C.c_void_p)]
+
+
+# rv_stamp.op, rv_stamp.orient (any OR); the caps on a pattern's dims, a context's patterns and a stamp list
+RV_STAMP_SET, RV_STAMP_CLEAR, RV_STAMP_COPY = range(3)
+RV_ORIENT_SWAP_XZ, RV_ORIENT_FLIP_X, RV_ORIENT_FLIP_Z = 1, 2, 4
+RV_PATTERN_MAX_DIM = 256
+RV_PATTERN_MAX = 256
+RV_STAMP_MAX = 1024
+
 STAT_FIELDS = ["traces", "primary", "shadow", "refl", "refl_shadow", "prepass_primary",
                "prepass_shadow", "cones", "cone_steps", "sphere_steps", "dda_steps",
                "csdf_checks", "tex_samples", "undef_hits", "gi_traces", "frames"]
@@ -204,6 +220,14 @@ SIGNATURES = [
     ("rv_world_fall_at", I32, [I32, I32, I32, P, C.POINTER(rv_voxel_box), I32, P, I64, C.POINTER(I64),
                                C.POINTER(U64), C.POINTER(rv_voxel_box), P, SZ]),
     ("rv_world_fall_info", I32, [P, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]),
+    ("rv_pattern_create", I32, [P, I32, I32, I32, P, SZ, C.POINTER(I32)]),
+    ("rv_pattern_capture", I32, [P, C.POINTER(rv_voxel_box), C.POINTER(I32)]),
+    ("rv_pattern_read", I32, [P, I32, C.POINTER(I32), P, SZ]),
+    ("rv_pattern_destroy", I32, [P, I32]),
+    ("rv_world_stamp", I32, [P, P, I32, C.POINTER(U64), C.POINTER(U64), C.POINTER(rv_voxel_box)]),
+    ("rv_world_stamp_at", I32, [I32, I32, I32, P, P, I32, P, I32, C.POINTER(U64), C.POINTER(U64)]),
+    ("rv_world_stamp_box", I32, [I32, I32, I32, P, I32, P, I32, P, P]),
+    ("rv_world_stamp_info", I32, [P, C.POINTER(U64), C.POINTER(U64), C.POINTER(I32), C.POINTER(U64)]),
     ("rv_texture_origin_set", I32, [P, I32, I32]),
     ("rv_texture_follow_scroll", I32, [P, I32]),
     ("rv_texture_origin_get", I32, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -11,7 +11,8 @@
 //   rv_bodies.cpp   swept box collision against the voxel window (rv_world_bodies_move);
 //   rv_detached.cpp voxels an edit left floating, found and cleared (rv_world_detached);
 //   rv_fall.cpp     detached components dropped in place (rv_world_fall);
-//   rv_shapes.cpp   ellipsoid and cylinder edits in one launch (rv_world_edit_shapes).
+//   rv_shapes.cpp   ellipsoid and cylinder edits in one launch (rv_world_edit_shapes);
+//   rv_stamp.cpp    patterns kept on the device and pasted, oriented, many per launch (rv_world_stamp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: RCCL is resolved at run time (rccl_load)
@@ -33,6 +34,7 @@
 #include <vector>
 
 #include "../../include/rvgrt/rv_frame.h"
+#include "../../include/rvgrt/rv_stamp.h"
 #ifndef RV_PIPE_DIAG
 #define RV_PIPE_DIAG 0   // per-wave diagnostics of the pipelined and flow launches (tools/pipe_waves.py, tools/flow_waves.py)
 #endif
@@ -363,6 +365,25 @@ struct rv_ctx {
     std::vector<rv_voxel_box> shape_box_h;
     DevBuf<rv_edit_shape> shape_list;
     DevBuf<unsigned long long> shape_counts;
+    // Patterns and rv_world_stamp (rv_stamp.cpp).  Both layouts of a live slot (A as given, T with x and z
+    // transposed: rv_stamp.h) have their padding bits zero.  A destroyed slot keeps its two allocations while they
+    // are small (PATTERN_KEEP each), for the next pattern that takes the slot: releasing device memory waits for
+    // the whole device, and a capture / stamp / destroy cycle (world_move) runs inside frame loops.  The made-ready
+    // stamps' stable host copy with the boxes of all stamps, its device copy, the two sums the kernel adds to,
+    // and rv_world_stamp_info's sums.
+    struct Pattern {
+        int32_t nx = 0, ny = 0, nz = 0;
+        DevBuf<uint32_t> a, t;
+        bool on = false;
+        bool live() const { return on; }
+    };
+    static constexpr size_t PATTERN_KEEP = (size_t)64 << 10;   // 256 slots x 2 layouts: 32 MiB at the most
+    Pattern patterns[RV_PATTERN_MAX];
+    std::vector<StampRec> stamp_h;
+    std::vector<rv_voxel_box> stamp_box_h;
+    DevBuf<StampRec> stamp_list;
+    DevBuf<unsigned long long> stamp_counts;
+    uint64_t stamp_calls = 0, stamp_applied = 0;
     int cur_slot = 0;
     uint64_t frame_seq = 0;
     std::string err;

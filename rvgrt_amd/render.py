@@ -324,6 +324,86 @@ def fall_at(log2_dims, bits, box, max_fall=0, cap=None, want_bits=True, in_place
     return comps[:min(int(cap), int(n.value))].copy(), int(n.value), int(v.value), _box_tuple(ch), out
 
 
+def pattern_bits(vox):
+    """A pattern in the ABI's layout from a bool array vox[z, y, x]: (dims (nx, ny, nz), uint32 words), rows
+    along x padded to 32-bit words, voxel (x, y, z) being bit x & 31 of word (x >> 5) + nwx * (y + ny * z)."""
+    vox = np.asarray(vox, bool)
+    if vox.ndim != 3 or 0 in vox.shape:
+        raise ValueError("a pattern is a non-empty bool array [z, y, x]")
+    nz, ny, nx = vox.shape
+    padded = np.zeros((nz, ny, 32 * ((nx + 31) // 32)), bool)
+    padded[:, :, :nx] = vox
+    return (nx, ny, nz), np.packbits(padded.ravel(), bitorder="little").view(np.uint32)
+
+
+def pattern_voxels(dims, words):
+    """The inverse of pattern_bits: the bool array [z, y, x] of a pattern of dims (nx, ny, nz)."""
+    nx, ny, nz = (int(v) for v in dims)
+    nwx = (nx + 31) // 32
+    w = np.ascontiguousarray(words, np.uint32)[:nwx * ny * nz]
+    return np.unpackbits(w.view(np.uint8), bitorder="little").reshape(nz, ny, 32 * nwx)[:, :, :nx].astype(bool)
+
+
+def _stamps(stamps):
+    """ctypes array of rv_stamp from tuples (pattern, op, orient, (x, y, z))."""
+    arr = (_lib.rv_stamp * max(len(stamps), 1))()
+    for i, s in enumerate(stamps):
+        if len(s) != 4 or len(s[3]) != 3:
+            raise ValueError("a stamp is (pattern, op, orient, (x, y, z))")
+        arr[i] = _lib.rv_stamp(int(s[0]), int(s[1]), int(s[2]), (C.c_int32 * 3)(*(int(v) for v in s[3])))
+    return arr
+
+
+def _patterns_host(patterns, need_bits):
+    """ctypes array of rv_pattern_host from bool arrays [z, y, x] (or, where only boxes are wanted, dims
+    (nx, ny, nz)); the second value keeps the words alive."""
+    arr = (_lib.rv_pattern_host * max(len(patterns), 1))()
+    keep = []
+    for i, p in enumerate(patterns):
+        if need_bits or isinstance(p, np.ndarray):
+            (nx, ny, nz), words = pattern_bits(p)
+            keep.append(words)
+            arr[i] = _lib.rv_pattern_host(nx, ny, nz, words.ctypes.data)
+        else:
+            arr[i] = _lib.rv_pattern_host(int(p[0]), int(p[1]), int(p[2]), None)
+    return arr, keep
+
+
+def stamp_at(log2_dims, bits, patterns, stamps):
+    """rv_world_stamp_at (host only): StateRender.world_stamp evaluated on the CPU by the row function the
+    kernel calls, over a copy of `bits` (RV_WORLD_BITS layout, log2_x >= 5).  patterns: bool arrays
+    [z, y, x] that stamp.pattern indexes.  Returns (bits_after, n_set, n_cleared)."""
+    L = _lib.load()
+    out = np.array(bits, np.uint32, copy=True).reshape(-1)
+    if out.size != (1 << sum(int(v) for v in log2_dims)) // 32:
+        raise ValueError("bits does not match log2_dims")
+    stamps, patterns = list(stamps), list(patterns)
+    lg = [int(v) for v in log2_dims]
+    pats, keep = _patterns_host(patterns, True)
+    a, b = C.c_uint64(), C.c_uint64()
+    st = L.rv_world_stamp_at(lg[0], lg[1], lg[2], _ptr(out), pats, len(patterns), _stamps(stamps), len(stamps),
+                             C.byref(a), C.byref(b))
+    if st != 0:
+        raise RvError(f"rv_world_stamp_at: {_lib.STATUS_NAMES.get(st, st)}")
+    return out, int(a.value), int(b.value)
+
+
+def stamp_box(log2_dims, patterns, stamps):
+    """rv_world_stamp_box (host only): (each, all) -- the clipped voxel box (x0, y0, z0, x1, y1, z1) of every
+    stamp in a world of these log2 dims (all zero for an empty one) and their union, world_stamp's
+    `changed`.  patterns: bool arrays [z, y, x] or dims (nx, ny, nz)."""
+    L = _lib.load()
+    stamps, patterns = list(stamps), list(patterns)
+    lg = [int(v) for v in log2_dims]
+    pats, keep = _patterns_host(patterns, False)
+    each = (rv_voxel_box * max(len(stamps), 1))()
+    u = rv_voxel_box()
+    st = L.rv_world_stamp_box(lg[0], lg[1], lg[2], pats, len(patterns), _stamps(stamps), len(stamps), each, C.byref(u))
+    if st != 0:
+        raise RvError(f"rv_world_stamp_box: {_lib.STATUS_NAMES.get(st, st)}")
+    return [_box_tuple(each[i]) for i in range(len(stamps))], _box_tuple(u)
+
+
 def rccl_path():
     """The RCCL of the HIP runtime this process uses: torch's bundled librccl
     when torch is already imported (the library then shares torch's runtime),
@@ -614,6 +694,70 @@ class StateRender:
                 done += k
             out["relight"] = gbox
         return out
+
+    def pattern_create(self, vox) -> int:
+        """rv_pattern_create: a bool array vox[z, y, x] (at most 256 per axis) becomes a pattern kept on the
+        device; returns its id, the lowest free slot."""
+        (nx, ny, nz), words = pattern_bits(vox)
+        pid = C.c_int32(-1)
+        self._check(self._L.rv_pattern_create(self._h, nx, ny, nz, _ptr(words), words.nbytes, C.byref(pid)),
+                    "rv_pattern_create")
+        return int(pid.value)
+
+    def pattern_capture(self, box) -> int:
+        """rv_pattern_capture: the voxels of the box (x0, y0, z0, x1, y1, z1) of the world become a new
+        pattern without leaving the device; a query, like world_detached.  Returns the id."""
+        b = _voxel_box(box)
+        pid = C.c_int32(-1)
+        self._check(self._L.rv_pattern_capture(self._h, C.byref(b), C.byref(pid)), "rv_pattern_capture")
+        return int(pid.value)
+
+    def pattern_read(self, pid) -> np.ndarray:
+        """rv_pattern_read: the pattern as a bool array [z, y, x]."""
+        dims = (C.c_int32 * 3)()
+        self._check(self._L.rv_pattern_read(self._h, int(pid), dims, None, 0), "rv_pattern_read")
+        nx, ny, nz = dims[:]
+        words = np.zeros(((nx + 31) // 32) * ny * nz, np.uint32)
+        self._check(self._L.rv_pattern_read(self._h, int(pid), dims, _ptr(words), words.nbytes), "rv_pattern_read")
+        return pattern_voxels((nx, ny, nz), words)
+
+    def pattern_destroy(self, pid):
+        """rv_pattern_destroy: the id is free again."""
+        self._check(self._L.rv_pattern_destroy(self._h, int(pid)), "rv_pattern_destroy")
+
+    def world_stamp(self, stamps):
+        """rv_world_stamp: patterns pasted into the world by one launch, in list order, a later stamp winning
+        voxel by voxel.  A stamp is (pattern id, op, orient, (x, y, z)): op RV_STAMP_SET / CLEAR / COPY,
+        orient any OR of RV_ORIENT_SWAP_XZ / FLIP_X / FLIP_Z (the 8 symmetries that keep y up), (x, y, z) the
+        world voxel of the oriented pattern's low corner; stamps are clipped to the window.  Ends like
+        world_edit over the union of their boxes.  Returns (n_set, n_cleared, changed): the voxels that turned
+        solid and empty, world before against world after, and that union box (relight over it)."""
+        stamps = list(stamps)
+        a, b, ch = C.c_uint64(), C.c_uint64(), rv_voxel_box()
+        self._check(self._L.rv_world_stamp(self._h, _stamps(stamps), len(stamps), C.byref(a), C.byref(b), C.byref(ch)),
+                    "rv_world_stamp")
+        return int(a.value), int(b.value), _box_tuple(ch)
+
+    def world_stamp_info(self):
+        """(calls, stamps, patterns_live, pattern_bytes): the world_stamp calls that launched, the stamps
+        they applied, the live patterns and their bytes."""
+        n, s, p, by = C.c_uint64(), C.c_uint64(), C.c_int32(), C.c_uint64()
+        self._check(self._L.rv_world_stamp_info(self._h, C.byref(n), C.byref(s), C.byref(p), C.byref(by)),
+                    "rv_world_stamp_info")
+        return int(n.value), int(s.value), int(p.value), int(by.value)
+
+    def world_move(self, box, delta):
+        """Matter moved sideways, up or down, composed of existing calls: pattern_capture of the voxel box,
+        then one world_stamp that clears the box's solid voxels at the old place and copies the box to
+        box + delta (the copy wins where the two overlap; what reaches beyond the window is lost), then
+        pattern_destroy.  The horizontal counterpart of world_fall.  Returns world_stamp's result."""
+        pid = self.pattern_capture(box)
+        try:
+            at = tuple(int(box[a]) for a in range(3))
+            to = tuple(int(box[a]) + int(delta[a]) for a in range(3))
+            return self.world_stamp([(pid, _lib.RV_STAMP_CLEAR, 0, at), (pid, _lib.RV_STAMP_COPY, 0, to)])
+        finally:
+            self.pattern_destroy(pid)
 
     def world_edit_info(self):
         """(edits, csdf_cells, last_full): calls that changed a voxel, the coarse
