@@ -69,6 +69,12 @@ rv_status rv_create(const rv_config* cfg, int32_t device, rv_ctx** out) {
     if (c->atlas.reserve(c, tiled.size() * 4)) return cleanup_fail(RV_ERR_OOM);
     hipMemcpy(c->atlas, tiled.data(), tiled.size() * 4, hipMemcpyHostToDevice);
     c->cfg.atlas_rgba8 = nullptr;
+    {   // the cones' first-sample offsets (FrameParams::cone_tab): constants of the library, not of a frame
+        float tab[CONE_TAB_FLOATS];
+        cone_offset_table(tab);
+        if (c->cone_tab.reserve(c, sizeof(tab))) return cleanup_fail(RV_ERR_OOM);
+        hipMemcpy(c->cone_tab, tab, sizeof(tab), hipMemcpyHostToDevice);
+    }
     // frame slot 0 (more with rv_set_frames_in_flight)
     int W = cfg->width, H = cfg->height;
     c->own_color_pitch = align256((size_t)W * 4);
@@ -695,6 +701,7 @@ static FrameParams make_params(rv_ctx* c, const rv_camera* cam, const float* vp,
     f.sun = sun_dir();
     f.time = time; f.jx = jx; f.jy = jy;
     cone_basis_scales(f.cone_k1, f.cone_k2);
+    f.cone_tab = c->cone_tab;
     for (int i = 0; i < 16; i++) {
         f.vp[i] = vp ? vp[i] : (i % 5 == 0 ? 1.0f : 0.0f);
         f.pvp[i] = pvp ? pvp[i] : f.vp[i];

@@ -190,7 +190,8 @@ struct rv_ctx {
     DevBuf<uint32_t> gi_tmp;      // update target (double buffer)
     size_t gi_bytes = 0;
     DevBuf<uint32_t> atlas;
-    DevBuf<uint32_t> tex;         // sampleTexture's tile table (World::tex), or empty
+    DevBuf<float> cone_tab;       // cone_offset_table(): the cones' first-sample offsets per axis normal
+    DevBuf<uint32_t> tex;        // sampleTexture's tile table (World::tex), or empty
     bool tex_tried = false;       // tex_table() ran (the table is built once per context)
     // frame images: the active slot's own ones unless bound
     uint32_t* color = nullptr; size_t color_pitch = 0; bool color_ext = false;
